@@ -16,7 +16,12 @@ events on the launch stream.  The two CFG halves of a step have identical inputs
 stored for both (0.21 of the 11.044 TFLOP; exact — config.shared_cfg_prefix, --no-share-prefix for the A/B); `achieved`
 still prices the reference's full 11.044 TFLOP per call (`roofline.flops_skipped_tflop_per_launch` and `achieved_issued` give the issued-work view;
 the breakdown: the shared prefix; the 5/9 (four-phase form) or 27/36 (nine tap planes over the source pixels, round 6) of the Upsample3D convs' products that their exact forms do not multiply; the 20/36 the Winograd F(2x2, 3x3) form of the deep ResNet convolutions does not multiply).  `cpu_baseline`: the oracle restatement of the reference's CPU path (kind "port")
-timed on this box's host cores on a bounded sample (a few UNet calls of the 50), extrapolated to T calls."""
+timed on this box's host cores on a bounded sample (a few UNet calls of the 50), extrapolated to T calls.
+
+A plain run only sets up, warms up, times the `--steps` passes, writes the outputs (`--dump-outputs DIR`) and prints the line.
+`cpu_baseline` and `extra_configs` (the other BASELINE configurations) are measured only under `--full`.
+`--dump-outputs DIR`: rank 0's finished latents of the last timed pass, (S, 4, 5, latent, latent) float32, as DIR/latents.npy
+(inputs and weights are seeded, so two builds can be compared output for output)."""
 import argparse
 import contextlib
 import json
@@ -289,10 +294,15 @@ def parse_args(argv=None):
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--ctx-len", type=int, default=85)
     ap.add_argument("--guidance", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and the secondary BASELINE configurations "
+                         "(off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write rank 0's finished latents of the last pass to DIR/latents.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the secondary BASELINE configurations (256x256 / 20 steps, FlintstonesSV batch 4, the stage-1 prior, "
-                         "the reference's context-row structure) that a default 1-GPU run times after the headline loop")
+                    help="with --full: skip the secondary BASELINE configurations (256x256 / 20 steps, FlintstonesSV batch 4, the "
+                         "stage-1 prior, the reference's context-row structure) timed after the headline loop")
     ap.add_argument("--context", choices=("dense", "reference"), default="dense",
                     help="context rows of the synthetic story: dense N(0,1) (the headline, SURVEY 8d) or the structure the "
                          "reference's context builders produce (2 dense images + 8 with identical rows, SURVEY F6; not the headline)")
@@ -393,6 +403,8 @@ def main(argv=None):
     a = parse_args(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a, argv)
 
@@ -516,6 +528,10 @@ def main(argv=None):
     with Watchdog(a.watchdog if dist_on else 0, f"rank {rank}: timed region ({a.steps} passes)"):
         dt, per_rank = timed_passes(timed_pass, a.steps, dist if dist_on else None, torch.cuda.synchronize,
                                     torch.device("cpu") if a.share_gpu else dev)   # (gloo gathers host tensors)
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "latents.npy"), loop.lat.detach().float().cpu().numpy())
 
     loop_rank1 = loop.rank1_runs is not None
     frames = 5 * S * a.steps * units
@@ -584,10 +600,11 @@ def main(argv=None):
             want = sum(0 if (a.ragged and r % 2) else S for r in range(world))
             assert got is not None and got.shape[0] == want and bool(torch.isfinite(got).all()), (None if got is None else got.shape, want)
             out["gathered_stories"] = int(got.shape[0])
-    if rank == 0 and world == 1 and not a.cfg_split and not a.no_extra_configs and not a.no_graph and a.latent == 64 and S == 1:
+    if (a.full and rank == 0 and world == 1 and not a.cfg_split and not a.no_extra_configs and not a.no_graph and a.latent == 64
+            and S == 1):
         del loop
         out["extra_configs"] = extra_configs(model)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, a.latent, a.ctx_len, T)
     if a.context != "dense":
         out["config"]["context_rows"] = "reference structure (2 dense images + 8 with identical rows, SURVEY F6): NOT the headline workload"

@@ -165,3 +165,31 @@ def test_bench_eight_ranks_share_one_gpu(hiplib):
     assert out["data"].startswith("INVALID (")
     assert out["config"]["parallelism"] == "story-replicas x8" and out["scaling"] == "weak"
     assert abs(out["value"] - 5 * 1 * 2 * 8 / (2 * out["ms_per_step"] * 1e-3)) < 1e-3 * out["value"]
+
+
+def test_bench_plain_run_dumps_outputs(hiplib, tmp_path):
+    """A plain one-GPU bench.py run (no --full) times the headline only and, with --dump-outputs, writes the finished latents of
+    its last timed pass; inputs and weights are seeded, so runs with different --steps / --warmup dump the same latents."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for steps, warmup in ((1, 0), (2, 1)):
+        d = str(tmp_path / f"s{steps}")
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--width", "64", "--latent", "16",
+                            "--ctx-len", "13", "--ddim-steps", "3", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0
+        assert "cpu_baseline" not in out and "extra_configs" not in out
+        assert sorted(os.listdir(d)) == ["latents.npy"]
+        lat = np.load(os.path.join(d, "latents.npy"))
+        assert lat.dtype == np.float32 and lat.shape == (1, 4, 5, 16, 16) and np.isfinite(lat).all()
+        dumps.append(lat)
+    np.testing.assert_allclose(dumps[0], dumps[1], rtol=1e-3, atol=1e-4)

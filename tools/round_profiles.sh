@@ -7,7 +7,7 @@ tag=${1:-r5}
 cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag
 mkdir -p "$out"
-python bench.py > "$out/bench_line.json" 2> "$out/bench.err"
+python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"
 bash tools/collect_profiles.sh "$tag" > "$out/collect.log" 2>&1
 bash tools/pmc_step.sh "${tag}_pmc" > "$out/pmc.log" 2>&1
 python tools/opprof.py --top 1000 > "$out/opprof.txt" 2>&1
