@@ -554,6 +554,25 @@ int rcdm_cfg_ddim_step(const void* eps, int32_t ld, float* latents, int32_t S, i
 int rcdm_cfg_pndm_step(const void* eps, int32_t ld, float* latents, float* history, int32_t S, int32_t reps,
                        int32_t frames, int32_t H, int32_t W, float guidance_scale, const float* table,
                        const int32_t* step_counter, void* stream);
+/* Fused classifier-free guidance + one step of diffusers 0.24.0 EulerDiscreteScheduler (s_churn = 0),
+ *   EulerAncestralDiscreteScheduler, LMSDiscreteScheduler (order 4) or DPMSolverMultistepScheduler (dpmsolver / dpmsolver++,
+ *   midpoint / heun, orders 1-3) — the remaining scheduler types RCDMsPipeline's constructor accepts (RCDMs_pipeline.py:72-79),
+ *   stepped at :497 with scale_model_input (:484) of the next step fused — driven by one table row per step:
+ *     e  = eps_u + s (eps_c - eps_u)                  (reps = 2; the eps row itself when reps = 1)
+ *     d  = px x + pe e                                (Euler / LMS: d = e;  DPM-Solver++: d = x0 = (x - sigma_t e) / alpha_t)
+ *     x' = a x + b d + w1 hist[s1] + w2 hist[s2] + w3 hist[s3] + c noise[*step_counter]
+ *     hist[slot_now] = d  (slot_now in 0..2);   latents = x';   model_in = cin_next x'
+ *   table: device fp32 [n_steps][16], row (*step_counter) =
+ *     (px, pe, a, b, w1, w2, w3, c, cin_next, slot_now, s1, s2, s3, cin, 0, 0)
+ *   as rcdms_amd.scheduler.*.sigma_table() lays it out; slots are small integers stored as floats, a slot outside 0..2
+ *   is not used, hist[s_k] is read only when w_k != 0 and the noise row only when c != 0; cin (this step's input scale) is
+ *   not read.  eps rows f16 [(reps*S)*f*H*W][ld] (uncond sample block first); latents, model_in fp32 (S,4,f,H,W), distinct
+ *   buffers — model_in is what rcdm_assemble_input reads for the next UNet evaluation; history: device fp32
+ *   [3][S*4*f*H*W], caller-owned, no initialisation needed; noise: device fp32 [n_steps][S*4*f*H*W] or NULL when no row
+ *   has c != 0.  step_counter as in rcdm_cfg_ddim_step. */
+int rcdm_cfg_sigma_step(const void* eps, int32_t ld, float* latents, float* model_in, float* history, const float* noise,
+                        int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W, float guidance_scale,
+                        const float* table, const int32_t* step_counter, void* stream);
 /* Stage-1 prior, per step of prior_pipeline.py:311-344.
  * rcdm_prior_assemble: tok[(b, l)] (f16, B*L rows of C) <- base rows, except l == time_row <- temb (one fp32 row of C);
  *   x16[b] (f16, E) <- latents[b % n_lat] (fp32): the `torch.cat([latents] * 2)` of :314 and the sequence concat of

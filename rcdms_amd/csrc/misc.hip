@@ -1,5 +1,5 @@
 // misc.hip — the small kernels around the UNet body: timestep embedding, tiny-M linears, input
-// assembly / layout conversion, fused CFG + DDIM update, weight repacking.
+// assembly / layout conversion, fused CFG + DDIM / PNDM / sigma-table updates, weight repacking.
 //
 // Replaces (reference): diffusers Timesteps/TimestepEmbedding via src/models/unet.py:100-103,383-389;
 // ResnetBlock3D.time_emb_proj src/models/resnet.py:191; the per-step torch.cat / chunk / scheduler.step
@@ -168,6 +168,70 @@ __global__ void cfg_pndm_kernel(const f16* __restrict__ eps, int ld, float* lat,
   if (mode == 2) x = hist[4 * total + idx];
   if (slot >= 0) hist[(size_t)slot * total + idx] = e;
   lat[idx] = k[0] * x + k[1] * mo;
+}
+
+// Classifier-free guidance + one step of the table-driven sigma-space / DPM-Solver update (rcdms_amd/scheduler.py
+// EulerDiscrete / EulerAncestralDiscrete / LMSDiscrete / DPMSolverMultistep .sigma_table(); row layout in rcdm.h).
+// Thread per spatial position (s, f, y, x): its 4 contiguous channels of each eps row are read once (one 8-byte load
+// when VEC), the CFG combine is done once, then the 4 channel planes of latents / history / noise / model_in are walked
+// (consecutive threads -> consecutive addresses in every plane).  A history slot is read only under a non-zero weight
+// and a noise row only under a non-zero c, so neither needs initialisation; slot indices outside 0..2 are ignored.
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_sigma_kernel(const f16* __restrict__ eps, int ld, float* __restrict__ lat,
+                                                        float* __restrict__ model_in, float* __restrict__ hist,
+                                                        const float* __restrict__ noise, int S, int reps, size_t fhw,
+                                                        float gs, const float* __restrict__ tab,
+                                                        const int* __restrict__ step) {
+  const size_t total = (size_t)S * 4 * fhw;
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (size_t)S * fhw) return;
+  const int s = (int)(p / fhw);
+  const size_t rem = p - (size_t)s * fhw;
+  float e[4];
+  const f16* eu = eps + p * ld;
+  if (VEC) {
+    const f16x4 u = *(const f16x4*)eu;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] = (float)u[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] = (float)eu[c];
+  }
+  if (reps == 2) {
+    const f16* ec = eps + ((size_t)S * fhw + p) * ld;
+    float v[4];
+    if (VEC) {
+      const f16x4 u = *(const f16x4*)ec;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = (float)u[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = (float)ec[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] = e[c] + gs * (v[c] - e[c]);
+  }
+  const int st = *step;
+  const float* k = tab + (size_t)st * 16;
+  const float px = k[0], pe = k[1], a = k[2], b = k[3], w1 = k[4], w2 = k[5], w3 = k[6], cn = k[7], cin = k[8];
+  const int slot = (int)k[9], s1 = (int)k[10], s2 = (int)k[11], s3 = (int)k[12];
+  const bool r1 = w1 != 0.f && s1 >= 0 && s1 < 3, r2 = w2 != 0.f && s2 >= 0 && s2 < 3, r3 = w3 != 0.f && s3 >= 0 && s3 < 3;
+  const bool rn = cn != 0.f && noise != nullptr, wr = slot >= 0 && slot < 3;
+  const float* nz = rn ? noise + (size_t)st * total : noise;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const size_t idx = ((size_t)s * 4 + c) * fhw + rem;
+    const float x = lat[idx];
+    const float d = px * x + pe * e[c];
+    float y = a * x + b * d;
+    if (r1) y += w1 * hist[(size_t)s1 * total + idx];
+    if (r2) y += w2 * hist[(size_t)s2 * total + idx];
+    if (r3) y += w3 * hist[(size_t)s3 * total + idx];
+    if (rn) y += cn * nz[idx];
+    if (wr) hist[(size_t)slot * total + idx] = d;
+    lat[idx] = y;
+    model_in[idx] = cin * y;
+  }
 }
 
 // Stage-1 prior, per-step sequence assembly.  tok rows (b, l) <- the step-independent rows of `base`, except row
@@ -398,6 +462,25 @@ int rcdm_cfg_pndm_step(const void* eps, int32_t ld, float* latents, float* histo
   const size_t total = (size_t)S * 4 * frames * H * W;
   hipLaunchKernelGGL(cfg_pndm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const f16*)eps, ld, latents, history, S, reps, frames, H, W, guidance_scale, table, step_counter);
+  return rcdm_check_launch();
+}
+
+int rcdm_cfg_sigma_step(const void* eps, int32_t ld, float* latents, float* model_in, float* history, const float* noise,
+                        int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W, float guidance_scale,
+                        const float* table, const int32_t* step_counter, void* stream) {
+  if (!eps || !latents || !model_in || !history || !table || !step_counter) return RCDM_EINVAL;
+  if (S <= 0 || (reps != 1 && reps != 2) || frames <= 0 || H <= 0 || W <= 0 || ld < 4) return RCDM_EINVAL;
+  const size_t fhw = (size_t)frames * H * W;
+  const size_t n = (size_t)S * fhw;
+  const bool vec = (ld & 3) == 0 && ((uintptr_t)eps & 7) == 0;
+  if (vec)
+    hipLaunchKernelGGL(cfg_sigma_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps, ld, latents, model_in, history, noise, S, reps, fhw, guidance_scale, table,
+                       step_counter);
+  else
+    hipLaunchKernelGGL(cfg_sigma_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps, ld, latents, model_in, history, noise, S, reps, fhw, guidance_scale, table,
+                       step_counter);
   return rcdm_check_launch();
 }
 

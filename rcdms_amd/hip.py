@@ -139,6 +139,7 @@ SYMBOLS = {
     "rcdm_rows_to_ncfhw": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "rcdm_cfg_ddim_step": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "rcdm_cfg_pndm_step": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "rcdm_cfg_sigma_step": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "rcdm_prior_assemble": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rcdm_cfg_unclip_step": (C.c_int, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
     "rcdm_load_timestep": (C.c_int, [_P, _P, _P, _I, _P]),
@@ -463,6 +464,11 @@ def rows_to_ncfhw(rows, ld, b, Cc, frames, H, W, out, stream=None):
 def cfg_pndm_step(eps, ld, lat, hist, S, reps, frames, H, W, gs, table, step, stream=None):
     _check(load().rcdm_cfg_pndm_step(eps, ld, lat, hist, S, reps, frames, H, W, gs, table, step,
                                      stream_ptr() if stream is None else stream), "rcdm_cfg_pndm_step")
+
+
+def cfg_sigma_step(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step, stream=None):
+    _check(load().rcdm_cfg_sigma_step(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step,
+                                      stream_ptr() if stream is None else stream), "rcdm_cfg_sigma_step")
 
 
 def cfg_ddim_step(eps, ld, lat, S, reps, frames, H, W, gs, coef, step, stream=None):

@@ -3,7 +3,7 @@
 Reference: the `for t in timesteps` body of RCDMsPipeline.__call__ (src/pipelines/RCDMs_pipeline.py:480-503):
 cat([latents]*2) -> cat([x, mask, masked_latents], 1) -> unet -> CFG combine -> scheduler.step.  Here one graph
 holds [this step's time_emb_proj rows from a per-schedule table | assemble the 9-channel rows | ~10^3 UNet kernels |
-fused CFG+DDIM update | step++]; the step index
+fused CFG + scheduler update | step++]; the step index
 and the coefficient table live in device memory, so the host issues exactly one hipGraphLaunch per step and never
 touches a parameter.  Generalised over the reference's hard-coded batch 1 / 64x64 (:408,:476) to S stories."""
 import torch
@@ -26,8 +26,11 @@ class DenoiseLoop:
         self.T = int(num_steps)
         dev = unet.device
         self.device = dev
+        # Euler / Euler-ancestral / LMS / DPM-Solver (rcdms_amd.scheduler): the whole schedule as rows of rcdm_cfg_sigma_step
+        self.sigma = hasattr(scheduler, "sigma_table")
         if not hasattr(scheduler, "alphas_cumprod"):
-            raise NotImplementedError(f"{type(scheduler).__name__}: only DDIM / PNDM schedulers have a fused HIP step")
+            raise NotImplementedError(f"{type(scheduler).__name__}: only rcdms_amd.scheduler's DDIM / PNDM / Euler / "
+                                      "Euler-ancestral / LMS / DPM-Solver schedulers have a fused HIP step")
         cfg = getattr(scheduler, "config", {})
         if getattr(cfg, "prediction_type", "epsilon") != "epsilon":
             raise NotImplementedError("only epsilon prediction")
@@ -37,14 +40,28 @@ class DenoiseLoop:
             raise NotImplementedError("DenoiseLoop: clip_sample / thresholding are not built into the fused DDIM step "
                                       "(the reference pipeline sets clip_sample=False)")
         scheduler.set_timesteps(int(num_steps), device=None)
-        ts = torch.as_tensor(scheduler.timesteps).to("cpu", torch.int64)
+        # fractional on the sigma path (Euler / LMS 'linspace', Karras sigmas): the time embedding takes them as they are
+        ts = torch.as_tensor(scheduler.timesteps).to("cpu", torch.float32 if self.sigma else torch.int64)
         self.timesteps = ts
         # PNDM (RCDMs_pipeline.py:72-79 accepts it; PLMS form): num_steps + 1 model evaluations, the multistep combination and
         # the update in rcdm_cfg_pndm_step from the scheduler's own per-call table
         self.pndm = hasattr(scheduler, "plms_table")
         self.T = len(ts)
-        self._pndm_next = 0   # PNDM only: the schedule row the PLMS history in self.hist is valid for (run() checks it)
-        if self.pndm:
+        self._pndm_next = 0   # multistep only: the schedule row the history in self.hist is valid for (run() checks it)
+        self.noise = None
+        self.model_in = None
+        if self.sigma:
+            self.pndm = False
+            self.coef = scheduler.sigma_table().to(dev)
+            n = stories * 4 * frames * height * width
+            self.hist = torch.empty(3, n, dtype=torch.float32, device=dev)      # the kernel needs no initialisation
+            # the table reads the history (LMS, DPM-Solver order >= 2): a run can only continue where the last one stopped
+            self.multistep = bool((self.coef[:, 4:7] != 0).any())
+            self._cin0 = float(self.coef[0, 13])
+            self.model_in = torch.zeros(stories, 4, frames, height, width, dtype=torch.float32, device=dev)
+            if scheduler.noise_needed:
+                self.noise = torch.zeros(self.T, stories, 4, frames, height, width, dtype=torch.float32, device=dev)
+        elif self.pndm:
             self.coef = scheduler.plms_table().to(dev)
             self.hist = torch.zeros(5, stories * 4 * frames * height * width, dtype=torch.float32, device=dev)
         else:
@@ -56,7 +73,8 @@ class DenoiseLoop:
             if getattr(cfg, "skip_prk_steps", None) is not None or any(a - b != ratio for a, b in zip(tl, tl[1:])):
                 raise NotImplementedError(
                     f"{type(scheduler).__name__}: its timesteps are not a DDIM schedule of stride {ratio} (a multistep "
-                    "scheduler?) — pass rcdms_amd.scheduler.DDIMScheduler or rcdms_amd.scheduler.PNDMScheduler")
+                    "scheduler?) — pass rcdms_amd.scheduler.DDIMScheduler, PNDMScheduler, EulerDiscreteScheduler, "
+                    "EulerAncestralDiscreteScheduler, LMSDiscreteScheduler or DPMSolverMultistepScheduler")
             ac = torch.as_tensor(scheduler.alphas_cumprod).double().cpu()
             final = torch.as_tensor(getattr(scheduler, "final_alpha_cumprod", 1.0)).double().cpu()
             rows = []
@@ -72,6 +90,7 @@ class DenoiseLoop:
         self.ctx_len = ctx_len
         S, R, f, H, W = stories, self.reps, frames, height, width
         self.lat = torch.zeros(S, 4, f, H, W, dtype=torch.float32, device=dev)
+        self.x_in = self.model_in if self.sigma else self.lat   # what the UNet input is assembled from
         self.mask = torch.zeros(R * S, 1, f, H, W, dtype=torch.float32, device=dev)
         self.masked = torch.zeros(R * S, 4, f, H, W, dtype=torch.float32, device=dev)
         # Two launch plans, built on first use: the general one, and the "shared prefix" one for the case the reference
@@ -103,7 +122,7 @@ class DenoiseLoop:
                 table = p.time_table(self.timesteps.tolist())
                 pre = [
                     lambda: hip.load_table_row(table.data_ptr(), self.step_dev.data_ptr(), p.tproj.data_ptr(), table.shape[1]),
-                    lambda: hip.assemble_input(self.lat.data_ptr(), self.mask.data_ptr() + m_off,
+                    lambda: hip.assemble_input(self.x_in.data_ptr(), self.mask.data_ptr() + m_off,
                                                self.masked.data_ptr() + k_off, S, 1, f, H, W, p.x_in.ptr, p.x_in.ld, CIN_PAD),
                 ]
                 post = [
@@ -118,7 +137,7 @@ class DenoiseLoop:
                 table = p.time_table(self.timesteps.tolist())
                 pre = [
                     lambda: hip.load_table_row(table.data_ptr(), self.step_dev.data_ptr(), p.tproj.data_ptr(), table.shape[1]),
-                    lambda: hip.assemble_input(self.lat.data_ptr(), self.mask.data_ptr(), self.masked.data_ptr(), S, R, f, H, W,
+                    lambda: hip.assemble_input(self.x_in.data_ptr(), self.mask.data_ptr(), self.masked.data_ptr(), S, R, f, H, W,
                                                p.x_in.ptr, p.x_in.ld, CIN_PAD),
                 ]
                 post = [
@@ -133,7 +152,11 @@ class DenoiseLoop:
     def _sched_step(self, eps_ptr, ld):
         """CFG combine + scheduler.step (RCDMs_pipeline.py:492-497) on the device-resident latents, row `step` of the table."""
         S, R, f, H, W = self.S, self.reps, self.f, self.H, self.W
-        if self.pndm:
+        if self.sigma:
+            hip.cfg_sigma_step(eps_ptr, ld, self.lat.data_ptr(), self.model_in.data_ptr(), self.hist.data_ptr(),
+                               0 if self.noise is None else self.noise.data_ptr(), S, R, f, H, W, self.gs,
+                               self.coef.data_ptr(), self.step_dev.data_ptr())
+        elif self.pndm:
             hip.cfg_pndm_step(eps_ptr, ld, self.lat.data_ptr(), self.hist.data_ptr(), S, R, f, H, W, self.gs, self.coef.data_ptr(),
                               self.step_dev.data_ptr())
         else:
@@ -164,13 +187,23 @@ class DenoiseLoop:
         for op in self._post:
             op()
 
-    def load(self, latents, mask, masked_latents, ctx):
-        """Stage the loop inputs in HBM (this is outside the timed hot loop: inputs resident when it starts)."""
+    def load(self, latents, mask, masked_latents, ctx, *, noise=None, generator=None):
+        """Stage the loop inputs in HBM (this is outside the timed hot loop: inputs resident when it starts).  latents: the
+        unit-variance initial noise (scaled by the scheduler's init_noise_sigma here).  noise / generator: Euler-ancestral
+        only — the T per-step noise tensors (T, S, 4, f, H, W), else drawn as T randn calls of shape (S, 4, f, H, W) in step
+        order from `generator`, on its device (what the scheduler's step() draws, one call per step)."""
         S, R = self.S, self.reps
         assert tuple(latents.shape) == tuple(self.lat.shape), (latents.shape, self.lat.shape)
         assert tuple(mask.shape) == tuple(self.mask.shape), (mask.shape, self.mask.shape)
         assert tuple(masked_latents.shape) == tuple(self.masked.shape)
         self.lat.copy_(latents.to(self.device, torch.float32) * self.init_noise_sigma)
+        if self.sigma:
+            torch.mul(self.lat, self._cin0, out=self.model_in)      # scale_model_input of step 0
+            if self.noise is not None:
+                if noise is None:
+                    noise = torch.stack([self._randn(generator) for _ in range(self.T)])
+                assert noise.numel() == self.noise.numel(), (tuple(noise.shape), tuple(self.noise.shape))
+                self.noise.copy_(noise.to(self.device, torch.float32).reshape(self.noise.shape))
         self.mask.copy_(mask.to(self.device, torch.float32))
         self.masked.copy_(masked_latents.to(self.device, torch.float32))
         # the CFG halves share their UNet input exactly when mask and masked latents repeat (the latents always do)
@@ -192,6 +225,16 @@ class DenoiseLoop:
         self._pndm_next = 0
         torch.cuda.current_stream(self.device).synchronize()
 
+    def _randn(self, generator):
+        """One N(0, I) draw of the latents' shape, as diffusers' randn_tensor makes it: on the generator's device, one
+        sample per generator when given a list of them."""
+        shape = tuple(self.lat.shape)
+        if isinstance(generator, (list, tuple)):
+            return torch.cat([torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=torch.float32).to(self.device)
+                              for g in generator])
+        gdev = generator.device if generator is not None else self.device
+        return torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
+
     def run(self, callback=None, callback_steps=1, use_graph=True, start=0, steps=None):
         """Run steps [start, start + steps) of the T-step schedule (default: all T) on the program's stream from the
         latents staged by load(); returns the latents (S,4,f,H,W) fp32 (device) after the last step run."""
@@ -200,10 +243,11 @@ class DenoiseLoop:
         stop = self.T if steps is None else start + int(steps)
         if not (0 <= start < stop <= self.T):
             raise ValueError(f"steps [{start}, {stop}) outside the {self.T}-step schedule")
-        if self.pndm and start not in (0, self._pndm_next):
-            # the PLMS step is stateful (four prediction slots + the saved first sample in self.hist): a run can only
-            # continue where the previous one stopped, or start over
-            raise ValueError(f"PNDM: run(start={start}) but the multistep history is valid for step {self._pndm_next} "
+        if (self.pndm or (self.sigma and self.multistep)) and start not in (0, self._pndm_next):
+            # the PLMS / LMS / DPM-Solver step is stateful (stored predictions in self.hist): a run can only continue where
+            # the previous one stopped, or start over
+            what = "PNDM" if self.pndm else "multistep scheduler"
+            raise ValueError(f"{what}: run(start={start}) but the multistep history is valid for step {self._pndm_next} "
                              "(continue there, or start at 0 after load())")
         cur = torch.cuda.current_stream(self.device)
         p.stream.wait_stream(cur)
@@ -211,12 +255,16 @@ class DenoiseLoop:
             if use_graph and self.graph is None:
                 # warm every kernel up once outside capture (lazy function loading), then restore the state
                 lat0 = self.lat.clone()
-                hist0 = self.hist.clone() if self.pndm else None   # (table row 0 overwrites slot 0 and the saved sample)
+                # (table row 0 overwrites a history slot, PNDM's saved sample, and the sigma path's model_in)
+                hist0 = self.hist.clone() if (self.pndm or self.sigma) else None
+                xin0 = self.model_in.clone() if self.sigma else None
                 self.step_dev.zero_()   # the warm-up step reads table / coefficient row `step`: keep it inside the tables
                 self._one_step_eager()
                 self.lat.copy_(lat0)
                 if hist0 is not None:
                     self.hist.copy_(hist0)
+                if xin0 is not None:
+                    self.model_in.copy_(xin0)
                 self.step_dev.zero_()
                 p.stream.synchronize()
                 self.graph = p.capture(pre=self._pre, post=self._post, skip_time=True)
@@ -228,7 +276,7 @@ class DenoiseLoop:
                     self._one_step_eager()
                 if callback is not None and i % callback_steps == 0:
                     p.stream.synchronize()
-                    callback(i, int(self.timesteps[i]), self.lat)
+                    callback(i, self.timesteps[i].item(), self.lat)
         self._pndm_next = stop
         cur.wait_stream(p.stream)
         return self.lat

@@ -1,4 +1,5 @@
-"""DDIM (and PNDM / UnCLIP) schedulers with the object protocol RCDMsPipeline expects from diffusers' DDIMScheduler
+"""DDIM (and PNDM / Euler / Euler-ancestral / LMS / DPM-Solver / UnCLIP) schedulers with the object protocol
+RCDMsPipeline expects from diffusers' DDIMScheduler
 (reference: built at stage2_batchtest_rcdms_model.py:247 from configs/testing.yaml:18-21, mutated at
 src/pipelines/RCDMs_pipeline.py:84-109, used at :455-456,483,497).
 
@@ -343,3 +344,516 @@ class UnCLIPScheduler:
                                     generator=generator)
             prev = prev + std.to(sample.dtype) * noise
         return UnCLIPSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Sigma-space and DPM-Solver schedulers (the other four types RCDMsPipeline's constructor accepts, RCDMs_pipeline.py:72-79).
+#
+# Arithmetic of diffusers==0.24.0 EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler and
+# DPMSolverMultistepScheduler (not vendored by the reference, not installed here: restated from the published classes —
+# "parity unpinned", pinned by closed-form known-answer tests in tests/test_sigma_schedulers.py).  Epsilon prediction only.
+# The sigmas are kept in fp64 (diffusers rounds them to fp32; the two agree to ~1e-7 relative).  Every update the pipeline
+# drives is linear in the sample, the CFG-combined noise prediction, at most three stored quantities and one noise tensor,
+# so each class also lays its schedule out as rows of the fused rcdm_cfg_sigma_step kernel (`sigma_table()`):
+#
+#   d  = px x + pe e                 (Euler / LMS: d = e;  DPM-Solver++: d = x0 = (x - sigma_t e) / alpha_t)
+#   x' = a x + b d + w1 hist[s1] + w2 hist[s2] + w3 hist[s3] + c noise[step];   hist[slot_now] = d
+#   model_in = cin_next x'           (scale_model_input of the next step)
+#
+# Row (16 fp32, computed in fp64): px, pe, a, b, w1, w2, w3, c, cin_next, slot_now, s1, s2, s3, cin, 0, 0 — slot_now -1:
+# d is not stored; cin: this step's scale_model_input factor (staged by DenoiseLoop.load for step 0; the kernel does not
+# read it).
+import inspect
+
+import numpy as np
+
+SIGMA_ROW = 16
+
+
+@dataclass
+class SigmaSchedulerOutput:
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+def _train_betas(c):
+    n = c.num_train_timesteps
+    if c.trained_betas is not None:
+        return torch.as_tensor(c.trained_betas, dtype=torch.float32)
+    if c.beta_schedule == "linear":
+        return torch.linspace(c.beta_start, c.beta_end, n, dtype=torch.float32)
+    if c.beta_schedule == "scaled_linear":
+        return torch.linspace(c.beta_start ** 0.5, c.beta_end ** 0.5, n, dtype=torch.float32) ** 2
+    raise NotImplementedError(f"beta_schedule {c.beta_schedule!r}: only 'linear', 'scaled_linear' and trained_betas")
+
+
+def _convert_to_karras(in_sigmas, n, sigma_min=None, sigma_max=None):
+    """Karras et al. (2022) eq. (5), rho = 7, between the given endpoints (default: the ends of in_sigmas)."""
+    lo = float(in_sigmas[-1]) if sigma_min is None else float(sigma_min)
+    hi = float(in_sigmas[0]) if sigma_max is None else float(sigma_max)
+    rho = 7.0
+    ramp = np.linspace(0, 1, n)
+    return (hi ** (1 / rho) + ramp * (lo ** (1 / rho) - hi ** (1 / rho))) ** rho
+
+
+def _sigma_to_t(sigma, log_sigmas):
+    """The (fractional) training timestep whose sigma is `sigma`: linear interpolation in log sigma."""
+    log_sigma = np.log(np.maximum(sigma, 1e-10))
+    dists = log_sigma - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    t = (1 - w) * low_idx + w * high_idx
+    return t.reshape(np.shape(sigma))
+
+
+class _SigmaScheduler:
+    """Shared part: config, betas, spacing, step index and the table form.  Subclasses set `_sig` (fp64 numpy, one sigma
+    per inference step plus the final one) and `timesteps` (fp32) in set_timesteps, and implement `_rows()`."""
+    order = 1
+    noise_needed = False
+    _timestep_dtype = torch.float32
+
+    def _setup(self, kw):
+        self._internal_dict = _FrozenDict(kw)
+        c = self.config
+        if c.prediction_type != "epsilon":
+            raise NotImplementedError(f"{type(self).__name__}: prediction_type {c.prediction_type!r} (epsilon only)")
+        if c.timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        self.betas = _train_betas(c)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        ac = self.alphas_cumprod.double().numpy()
+        self._train_sig = np.sqrt((1 - ac) / ac)          # sigma of every training timestep, fp64
+        self.num_inference_steps = None
+        self._step_index = None
+        self._sig = np.concatenate([self._train_sig[::-1], [0.0]])
+        self.timesteps = torch.from_numpy(np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps)[::-1].copy()
+                                          ).to(torch.float32)
+
+    @property
+    def config(self):
+        return self._internal_dict
+
+    @classmethod
+    def from_config(cls, config, **kwargs):
+        """`cls(**config)` without the keys cls does not take (e.g. DDIM's clip_sample), then `kwargs` on top."""
+        params = inspect.signature(cls.__init__).parameters
+        kw = {k: v for k, v in dict(config).items() if k in params and k != "self"}
+        kw.update(kwargs)
+        return cls(**kw)
+
+    @property
+    def sigmas(self):
+        return torch.from_numpy(self._sig.astype(np.float32))
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def _init_step_index(self, timestep):
+        cand = (self.timesteps == float(timestep)).nonzero()
+        if len(cand) == 0:
+            self._step_index = len(self.timesteps) - 1
+        else:
+            self._step_index = int(cand[1 if len(cand) > 1 else 0])
+
+    def _spaced(self, n):
+        """fp32 inference timesteps of the Euler / LMS family (descending; fractional for 'linspace')."""
+        c = self.config
+        N = c.num_train_timesteps
+        if c.timestep_spacing == "linspace":
+            return np.linspace(0, N - 1, n, dtype=np.float32)[::-1].copy()
+        if c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (N // n)).round()[::-1].copy().astype(np.float32)
+            return ts + np.float32(c.steps_offset)
+        return np.arange(N, 0, -N / n).round().copy().astype(np.float32) - np.float32(1)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        if num_inference_steps > self.config.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
+                             f"`self.config.train_timesteps`: {self.config.num_train_timesteps}")
+        self.num_inference_steps = int(num_inference_steps)
+        ts, sig = self._schedule(self.num_inference_steps)
+        self._sig = sig
+        t = torch.from_numpy(np.ascontiguousarray(ts)).to(self._timestep_dtype)
+        self.timesteps = t.to(device) if device is not None else t
+        self._step_index = None
+        self._reset_state()
+
+    def _reset_state(self):
+        pass
+
+    def _karras(self, sig, n):
+        return _convert_to_karras(sig, n)
+
+    def _sigma_space_schedule(self, n, karras):
+        ts = self._spaced(n)
+        sig = np.interp(ts.astype(np.float64), np.arange(0, len(self._train_sig)), self._train_sig)
+        if karras:
+            sig = self._karras(sig, n)
+            ts = np.array([_sigma_to_t(s, np.log(self._train_sig)) for s in sig]).astype(np.float32)
+        return ts, np.concatenate([sig, [0.0]])
+
+    @property
+    def init_noise_sigma(self):
+        smax = float(self._sig.max())
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return smax
+        return (smax ** 2 + 1) ** 0.5
+
+    def scale_model_input(self, sample, timestep=None):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return sample / ((self._sig[self._step_index] ** 2 + 1) ** 0.5)
+
+    def _cin(self, i):
+        """scale_model_input factor of step i (1 after the last step: the final sample is returned as is)."""
+        return 1.0 / (self._sig[i] ** 2 + 1) ** 0.5 if i < len(self.timesteps) else 1.0
+
+    def sigma_table(self):
+        """fp32 [num_steps][16] rows of rcdm_cfg_sigma_step for the current schedule (layout: module comment above)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        rows = []
+        for i, r in enumerate(self._rows()):
+            row = [0.0] * SIGMA_ROW
+            px, pe, a, b, w, c, slot, ss = r
+            w, ss = list(w) + [0.0] * (3 - len(w)), list(ss) + [0] * (3 - len(ss))
+            row[0:9] = [px, pe, a, b, w[0], w[1], w[2], c, self._cin(i + 1)]
+            row[9:14] = [slot, ss[0], ss[1], ss[2], self._cin(i)]
+            rows.append(row)
+        return torch.tensor(np.array(rows, dtype=np.float64), dtype=torch.float32)
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """Euler (Karras et al. 2022, Algorithm 2) in sigma space, diffusers 0.24.0 `EulerDiscreteScheduler` with s_churn = 0
+    (the only value the pipeline passes: prepare_extra_step_kwargs forwards just `generator`):
+      x' = x + (sigma_next - sigma) (x - x0) / sigma,   x0 = x - sigma e;   sigmas interpolated at the (float) timesteps,
+    0 appended; optional Karras sigmas.  interpolation_type 'log_linear', timestep_type 'continuous' and s_churn > 0 raise."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False,
+                 sigma_min=None, sigma_max=None, timestep_spacing="linspace", timestep_type="discrete", steps_offset=0):
+        self._setup(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                         beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type,
+                         interpolation_type=interpolation_type, use_karras_sigmas=use_karras_sigmas, sigma_min=sigma_min,
+                         sigma_max=sigma_max, timestep_spacing=timestep_spacing, timestep_type=timestep_type,
+                         steps_offset=steps_offset))
+        if interpolation_type != "linear" or timestep_type != "discrete":
+            raise NotImplementedError("EulerDiscreteScheduler: interpolation_type 'linear' / timestep_type 'discrete' only")
+        self.use_karras_sigmas = use_karras_sigmas
+
+    def _karras(self, sig, n):
+        return _convert_to_karras(sig, n, self.config.sigma_min, self.config.sigma_max)
+
+    def _schedule(self, n):
+        return self._sigma_space_schedule(n, self.config.use_karras_sigmas)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
+             generator=None, return_dict=True):
+        if s_churn != 0.0:
+            raise NotImplementedError("EulerDiscreteScheduler: s_churn > 0 (stochastic Euler) is not built")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma, nxt = self._sig[self._step_index], self._sig[self._step_index + 1]
+        x0 = sample - sigma * model_output
+        prev = sample + (sample - x0) / sigma * (nxt - sigma)
+        self._step_index += 1
+        return SigmaSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+    def _rows(self):
+        s = self._sig
+        return [(0.0, 1.0, 1.0, s[i + 1] - s[i], (), 0.0, -1, ()) for i in range(len(self.timesteps))]
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """Ancestral Euler, diffusers 0.24.0 `EulerAncestralDiscreteScheduler`: from sigma to sigma_next via
+      sigma_up = sqrt(sigma_next^2 (sigma^2 - sigma_next^2) / sigma^2),  sigma_down = sqrt(sigma_next^2 - sigma_up^2),
+      x' = x + (sigma_down - sigma) e + sigma_up n,   n ~ N(0, I): one fresh randn of the sample's shape per step, drawn
+    from the caller's generator (also at the last step, where sigma_up = 0).  No Karras option in this version."""
+    noise_needed = True
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0):
+        self._setup(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                         beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type,
+                         timestep_spacing=timestep_spacing, steps_offset=steps_offset))
+
+    def _schedule(self, n):
+        return self._sigma_space_schedule(n, False)
+
+    def _up_down(self, i):
+        s, nxt = self._sig[i], self._sig[i + 1]
+        up = (nxt ** 2 * (s ** 2 - nxt ** 2) / s ** 2) ** 0.5
+        return up, max(nxt ** 2 - up ** 2, 0.0) ** 0.5
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
+        """noise: the step's N(0, I) draw, if the caller has it; else randn of model_output's shape from `generator`
+        (on the generator's device when that is the CPU, as diffusers' randn_tensor)."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = self._sig[self._step_index]
+        up, down = self._up_down(self._step_index)
+        x0 = sample - sigma * model_output
+        prev = sample + (sample - x0) / sigma * (down - sigma)
+        if noise is None:
+            dev = model_output.device
+            gdev = generator.device if generator is not None else dev
+            noise = torch.randn(model_output.shape, dtype=model_output.dtype, device=gdev, generator=generator).to(dev)
+        prev = prev + noise * up
+        self._step_index += 1
+        return SigmaSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+    def _rows(self):
+        rows = []
+        for i in range(len(self.timesteps)):
+            up, down = self._up_down(i)
+            rows.append((0.0, 1.0, 1.0, down - self._sig[i], (), up, -1, ()))
+        return rows
+
+
+class LMSDiscreteScheduler(_SigmaScheduler):
+    """Linear multistep in sigma space, diffusers 0.24.0 `LMSDiscreteScheduler` with step(order=4):
+      x' = x + sum_k c_k d_{i-k},   d = (x - x0) / sigma = e,   c_k = integral over [sigma_i, sigma_{i+1}] of the Lagrange
+    basis polynomial of node sigma_{i-k} on the nodes sigma_i .. sigma_{i-m+1}, m = min(i + 1, order).  diffusers integrates
+    with scipy.integrate.quad (epsrel 1e-4); here the polynomial is integrated exactly (numpy.polynomial)."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, use_karras_sigmas=False, prediction_type="epsilon", timestep_spacing="linspace",
+                 steps_offset=0):
+        self._setup(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                         beta_schedule=beta_schedule, trained_betas=trained_betas, use_karras_sigmas=use_karras_sigmas,
+                         prediction_type=prediction_type, timestep_spacing=timestep_spacing, steps_offset=steps_offset))
+        self.use_karras_sigmas = use_karras_sigmas
+        self.derivatives = []
+        self.set_timesteps(num_train_timesteps)
+
+    def _schedule(self, n):
+        return self._sigma_space_schedule(n, self.config.use_karras_sigmas)
+
+    def _reset_state(self):
+        self.derivatives = []
+
+    def get_lms_coefficient(self, order, t, current_order):
+        """Exact integral of the Lagrange basis polynomial of node sigma[t - current_order] from sigma[t] to sigma[t + 1]."""
+        s = self._sig
+        poly = np.polynomial.Polynomial([1.0])
+        for k in range(order):
+            if k != current_order:
+                poly = poly * np.polynomial.Polynomial([-s[t - k], 1.0]) / (s[t - current_order] - s[t - k])
+        anti = poly.integ()
+        return float(anti(s[t + 1]) - anti(s[t]))
+
+    def _coeffs(self, i, order=4):
+        m = min(i + 1, order)
+        return [self.get_lms_coefficient(m, i, k) for k in range(m)]
+
+    def step(self, model_output, timestep, sample, order=4, return_dict=True):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = self._sig[self._step_index]
+        x0 = sample - sigma * model_output
+        self.derivatives.append((sample - x0) / sigma)
+        if len(self.derivatives) > order:
+            self.derivatives.pop(0)
+        coeffs = self._coeffs(self._step_index, order)
+        prev = sample + sum(c * d for c, d in zip(coeffs, reversed(self.derivatives)))
+        self._step_index += 1
+        return SigmaSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+    def _rows(self):
+        n = len(self.timesteps)
+        rows = []
+        for i in range(n):
+            c = self._coeffs(i)
+            slot = i % 3 if i + 1 < n else -1      # the derivative is read by the next three steps
+            ss = [(i - k) % 3 for k in range(1, len(c))]
+            rows.append((0.0, 1.0, 1.0, c[0], c[1:], 0.0, slot, ss))
+        return rows
+
+
+class DPMSolverMultistepScheduler(_SigmaScheduler):
+    """DPM-Solver / DPM-Solver++ multistep (Lu et al. 2022), diffusers 0.24.0 `DPMSolverMultistepScheduler`:
+    algorithm_type 'dpmsolver++' (model output converted to x0 = (x - sigma_t e) / alpha_t) and 'dpmsolver' (e itself),
+    solver_type 'midpoint' / 'heun', solver_order 1-3, lower_order_final / euler_at_final (below 15 steps the last two
+    steps drop to orders 1 and 2), integer timesteps linspace(0, last_t - 1, n + 1).round()[::-1][:-1] ('linspace'), and
+    Karras sigmas (timesteps then the rounded _sigma_to_t of each).  alpha_t = 1 / sqrt(sigma^2 + 1), sigma_t = sigma
+    alpha_t, lambda = log(alpha_t / sigma_t).
+
+    Final sigma: 0.24.0 appends the sigma of training timestep 0 (Karras: the last Karras sigma, which is the same value),
+    not 0 — later diffusers releases made that configurable (final_sigmas_type).  This class follows 0.24.0, so the result
+    keeps the small noise level sigma(t=0).  Where a step has h = 0 (Karras: the appended sigma equals the last one) the
+    h -> 0 limit is used, the sample unchanged — what 0.24.0 computes for first and second order midpoint steps (its
+    heun and third-order forms divide 0 by 0 there).
+    Refused: sde-dpmsolver / sde-dpmsolver++, thresholding, prediction types other than epsilon, use_lu_lambdas."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                 dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++",
+                 solver_type="midpoint", lower_order_final=True, euler_at_final=False, use_karras_sigmas=False,
+                 use_lu_lambdas=False, lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace",
+                 steps_offset=0):
+        if algorithm_type == "deis":            # diffusers maps these onto the nearest built form
+            algorithm_type = "dpmsolver++"
+        if solver_type in ("logrho", "bh1", "bh2"):
+            solver_type = "midpoint"
+        self._setup(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                         beta_schedule=beta_schedule, trained_betas=trained_betas, solver_order=solver_order,
+                         prediction_type=prediction_type, thresholding=thresholding,
+                         dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+                         algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+                         euler_at_final=euler_at_final, use_karras_sigmas=use_karras_sigmas, use_lu_lambdas=use_lu_lambdas,
+                         lambda_min_clipped=lambda_min_clipped, variance_type=variance_type,
+                         timestep_spacing=timestep_spacing, steps_offset=steps_offset))
+        if algorithm_type in ("sde-dpmsolver", "sde-dpmsolver++"):
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: {algorithm_type} (SDE variants) is not built")
+        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            raise NotImplementedError(f"{algorithm_type} does is not implemented for {self.__class__}")
+        if solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"{solver_type} does is not implemented for {self.__class__}")
+        if thresholding:
+            raise NotImplementedError("DPMSolverMultistepScheduler: thresholding is not built")
+        if use_lu_lambdas:
+            raise NotImplementedError("DPMSolverMultistepScheduler: use_lu_lambdas is not built")
+        if variance_type is not None:
+            raise NotImplementedError("DPMSolverMultistepScheduler: learned variance is not built")
+        if solver_order not in (1, 2, 3):
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: solver_order {solver_order} (1-3)")
+        self.use_karras_sigmas = use_karras_sigmas
+        self._reset_state()
+
+    init_noise_sigma = 1.0    # a plain attribute here, not the sigma-space property
+    _timestep_dtype = torch.int64
+
+    def _reset_state(self):
+        self.model_outputs = [None] * self.config.solver_order
+        self.lower_order_nums = 0
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _cin(self, i):
+        return 1.0
+
+    def _schedule(self, n):
+        c = self.config
+        N = c.num_train_timesteps
+        ac = self.alphas_cumprod.double()
+        lam = torch.log(ac.sqrt()) - torch.log((1 - ac).sqrt())
+        clipped = int(torch.searchsorted(torch.flip(lam, [0]), torch.tensor(float(c.lambda_min_clipped), dtype=lam.dtype)))
+        last = N - clipped
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, last - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (last // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
+        else:
+            ts = np.arange(last, 0, -N / n).round().copy().astype(np.int64) - 1
+        sig = self._train_sig
+        if c.use_karras_sigmas:
+            ks = _convert_to_karras(sig[::-1].copy(), n)
+            ts = np.array([_sigma_to_t(s, np.log(sig)) for s in ks]).round().astype(np.int64)
+            sig_out = np.concatenate([ks, ks[-1:]])
+        else:
+            sig_out = np.concatenate([np.interp(ts.astype(np.float64), np.arange(0, len(sig)), sig), [sig[0]]])
+        return ts, sig_out
+
+    def set_timesteps(self, num_inference_steps=None, device=None):
+        super().set_timesteps(num_inference_steps, device)
+        self.num_inference_steps = len(self.timesteps)
+
+    @staticmethod
+    def _alpha_sigma(sigma):
+        alpha = 1.0 / (sigma ** 2 + 1) ** 0.5
+        return alpha, sigma * alpha
+
+    def _lam(self, i):
+        a, s = self._alpha_sigma(self._sig[i])
+        return np.log(a) - np.log(s)
+
+    def _order_at(self, i):
+        """The order 0.24.0's step() uses at step i (lower_order_nums = min(i, solver_order) there)."""
+        c, n = self.config, len(self.timesteps)
+        final = i == n - 1 and (c.euler_at_final or (c.lower_order_final and n < 15))
+        second = i == n - 2 and c.lower_order_final and n < 15
+        if c.solver_order == 1 or i < 1 or final:
+            return 1
+        if c.solver_order == 2 or i < 2 or second:
+            return 2
+        return 3
+
+    def _convert(self, i):
+        """(px, pe) of the converted model output at step i."""
+        if self.config.algorithm_type == "dpmsolver":
+            return 0.0, 1.0
+        a, s = self._alpha_sigma(self._sig[i])
+        return 1.0 / a, -s / a
+
+    def _update(self, i, order, sample, ms):
+        """The solver update of step i from `sample` and the converted model outputs ms (newest last), restated from
+        dpm_solver_first_order_update / multistep_dpm_solver_second_order_update / ..._third_order_update.  Linear in
+        sample and ms, so sigma_table() evaluates it on unit vectors."""
+        c = self.config
+        pp = c.algorithm_type == "dpmsolver++"
+        a_t, s_t = self._alpha_sigma(self._sig[i + 1])
+        a_0, s_0 = self._alpha_sigma(self._sig[i])
+        h = self._lam(i + 1) - self._lam(i)
+        em = np.expm1(-h) if pp else np.expm1(h)                   # e^{-h} - 1 (++) or e^{h} - 1
+        base = (s_t / s_0) * sample if pp else (a_t / a_0) * sample
+        k0 = -a_t * em if pp else -s_t * em
+        m0 = ms[-1]
+        if order == 1:
+            return base + k0 * m0
+        if h == 0:      # the h -> 0 limit (Karras' repeated last sigma): sample unchanged
+            return base + k0 * m0
+        g1 = em / h + 1.0 if pp else em / h - 1.0                  # (e^{-h} - 1) / h + 1  |  (e^{h} - 1) / h - 1
+        h0 = self._lam(i) - self._lam(i - 1)
+        inv_r0 = h / h0
+        if order == 2:
+            D1 = inv_r0 * (m0 - ms[-2])
+            if c.solver_type == "midpoint":
+                return base + k0 * m0 + 0.5 * k0 * D1
+            return base + k0 * m0 + (a_t * g1 if pp else -s_t * g1) * D1
+        h1 = self._lam(i - 1) - self._lam(i - 2)
+        r0, r1 = h0 / h, h1 / h
+        D1_0, D1_1 = inv_r0 * (m0 - ms[-2]), (1.0 / r1) * (ms[-2] - ms[-3])
+        D1 = D1_0 + (r0 / (r0 + r1)) * (D1_0 - D1_1)
+        D2 = (1.0 / (r0 + r1)) * (D1_0 - D1_1)
+        if pp:
+            g2 = (em + h) / h ** 2 - 0.5
+            return base + k0 * m0 + a_t * g1 * D1 - a_t * g2 * D2
+        g2 = (em - h) / h ** 2 - 0.5
+        return base + k0 * m0 - s_t * g1 * D1 - s_t * g2 * D2
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        px, pe = self._convert(i)
+        m = px * sample + pe * model_output
+        self.model_outputs = self.model_outputs[1:] + [m]
+        order = self._order_at(i)
+        prev = self._update(i, order, sample, [x for x in self.model_outputs if x is not None][-order:])
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
+        self._step_index += 1
+        return SigmaSchedulerOutput(prev_sample=prev) if return_dict else (prev,)
+
+    def _rows(self):
+        n = len(self.timesteps)
+        keep = self.config.solver_order - 1          # how many past outputs a later step may read
+        rows = []
+        for i in range(n):
+            order = self._order_at(i)
+            e = np.eye(4)
+            v = self._update(i, order, e[0], [e[3], e[2], e[1]][-order:])   # sample, m_{i-2}, m_{i-1}, m_i
+            px, pe = self._convert(i)
+            w = [v[2], v[3]][:order - 1]
+            slot = i % 3 if keep > 0 and i + 1 < n else -1
+            ss = [(i - k) % 3 for k in range(1, order)]
+            rows.append((px, pe, v[0], v[1], w, 0.0, slot, ss))
+        return rows

@@ -3,7 +3,7 @@
 `local_feature`, same constructor (RCDMs_pipeline.py:64-80) and `__call__` signature (:374-398).
 
 What runs where:
-  * the denoising loop (:455-503) — T x [UNet + CFG + DDIM] — runs on MI355X as replays of one captured hipGraph
+  * the denoising loop (:455-503) — T x [UNet + CFG + scheduler step] — runs on MI355X as replays of one captured hipGraph
     (rcdms_amd.sampler.DenoiseLoop); this is the hot path and has no torch fallback;
   * prompt / VAE / context-stack glue around it calls the user-supplied torch modules exactly as the reference
     does (they are inputs of this pipeline, not part of it).
@@ -230,8 +230,9 @@ class RCDMsPipeline:
 
     # ---- the hot loop ----------------------------------------------------------------------------------------------
     def denoise(self, latents, mask, masked_latents, context, num_inference_steps, guidance_scale, callback=None,
-                callback_steps=1):
-        """latents (S,4,f,h,w); mask (R*S,1,f,h,w); masked_latents (R*S,4,f,h,w); context (R*S*f, L, D)."""
+                callback_steps=1, generator=None):
+        """latents (S,4,f,h,w) unit-variance noise (DenoiseLoop.load applies init_noise_sigma); mask (R*S,1,f,h,w);
+        masked_latents (R*S,4,f,h,w); context (R*S*f, L, D); generator: the per-step noise of Euler-ancestral."""
         S, _, f, h, w = latents.shape
         key = (S, f, h, w, context.shape[1], float(guidance_scale), int(num_inference_steps), id(self.scheduler),
                id(self.unet), self.unet._weights_gen)
@@ -240,7 +241,7 @@ class RCDMsPipeline:
                                      num_inference_steps)
             self._loop_key = (S, f, h, w, context.shape[1], float(guidance_scale), int(num_inference_steps),
                               id(self.scheduler), id(self.unet), self.unet._weights_gen)
-        self._loop.load(latents, mask, masked_latents, context)
+        self._loop.load(latents, mask, masked_latents, context, generator=generator)
         return self._loop.run(callback=callback, callback_steps=callback_steps)
 
     @torch.no_grad()
@@ -293,8 +294,10 @@ class RCDMsPipeline:
                 bar.update()
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, lat)
-            final = self.denoise(latents, mask5, masked_latents, context, num_inference_steps, guidance_scale,
-                                 callback=on_step if (callback is not None) else None, callback_steps=1)
+            # prepare_latents applied init_noise_sigma (as the reference does); DenoiseLoop.load applies it itself
+            final = self.denoise(latents / self.scheduler.init_noise_sigma, mask5, masked_latents, context,
+                                 num_inference_steps, guidance_scale, callback=on_step if (callback is not None) else None,
+                                 callback_steps=1, generator=generator)
             if callback is None:
                 bar.update(num_inference_steps)
 
