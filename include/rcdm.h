@@ -364,7 +364,14 @@ int rcdm_layernorm(const rcdm_layernorm_desc* d, const void* x, const float* gam
  *   replaces CrossAttention._attention attention.py:170-199 (+ reshape_heads_to_batch_dim :93-105):
  *   self-attention over the hw latent patches of one frame and cross-attention over the L_text
  *   context rows of that frame.  Q rows [batch*Lq][ldq] with head h at columns [h*d, (h+1)*d);
- *   K,V rows [batch*Lk][ldk|ldv]; out [batch*Lq][ldo].  d % 8 == 0, d <= 160.
+ *   K,V rows [batch*Lk][ldk|ldv]; out [batch*Lq][ldo].  Head dim: d % 8 == 0 for d <= 160; d % 64 == 0 for
+ *   160 < d <= 512 (rcdm_flash_attn, and rcdm_flash_attn_masked with key_valid == NULL and causal == 0, only: a mask at
+ *   d > 160 is RCDM_ESHAPE, as is d > 512).  The wide heads are the one 512-channel head of the SD-1.5 VAE mid block
+ *   (diffusers 0.24.0 AutoencoderKL, UNetMidBlock2D attention over the h*w latent pixels of an image) at any image size:
+ *   a kernel of its own (csrc/attn_wide.hip: 4 waves x 32 queries per block, one wave per SIMD), same layout rules
+ *   (ldq / ldk / ldv % 8 == 0, ldo % 4 == 0, column views of wider buffers allowed), no workspace, capturable.  Its
+ *   softmax reference is fixed per pass over the keys (first-tile row max; a second pass on the exact row max when a
+ *   query's scores leave the f16 range of exp2 around it), so it has no score-range limit and ignores `flags`.
  *   Range: scaled scores |scale * log2(e) * q.k| < 2^15 (the d = 40, Lk >= 256 kernel keeps its running max as an f16 inside
  *   the Q fragment and re-rounds Q * scale * log2(e) to f16: relative error ln2 * 2^-12 * |scaled score| on a probability).
  *   A caller that cannot bound its scores below that sets RCDM_ATTN_WIDE_RANGE in `flags` (or the environment sets
@@ -488,9 +495,9 @@ int rcdm_rowchain(const rcdm_rowchain_desc* d, const void* a_in, const void* res
 
 /* ------------------------------------------------------------------------------------------------
  * Row softmax: y[m][n] = softmax over n of (scale * x[m][n]); f16 rows, fp32 math, N % 8 == 0, N <= 4096, scale > 0.
- *   With two rcdm_gemm calls (scores = Q K^T, out = P V^T^T) it is the attention of heads too wide for
- *   rcdm_flash_attn: the single 512-channel head of the SD-1.5 VAE mid block (diffusers 0.24.0 AutoencoderKL,
- *   called at RCDMs_pipeline.py:281,429 — SURVEY §8f N3).
+ *   With two rcdm_gemm calls (scores = Q K^T, out = P V^T^T) it is the score-buffer form of the single 512-channel
+ *   head of the SD-1.5 VAE mid block (diffusers 0.24.0 AutoencoderKL, called at RCDMs_pipeline.py:281,429 — SURVEY §8f
+ *   N3) up to 4096 latent pixels; above, rcdm_flash_attn at d = 512 (rcdms_amd/vae.py, mid_attention_form).
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_softmax_rows(int32_t M, int32_t N, int32_t ldx, int32_t ldy, float scale, const void* x, void* y, void* stream);
 

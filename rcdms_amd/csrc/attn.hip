@@ -15,6 +15,7 @@
 // scatter on the way in and no cross-lane shuffle on the way out.
 #include <stdlib.h>
 #include "common.h"
+#include "attn_wide.h"
 
 long long* g_attn_trace = nullptr;  // rcdm_debug_set_attn_trace (read by -DRCDM_ATTN_TRACE builds only)
 
@@ -833,10 +834,28 @@ int rcdm_flash_attn_masked(const rcdm_attn_desc* d, const void* Q, const void* K
                            const unsigned char* key_valid, int32_t causal, void* out, void* stream_) {
   if (!d || !Q || !K || !V || !out) return RCDM_EINVAL;
   if (d->batch <= 0 || d->heads <= 0 || d->Lq <= 0 || d->Lk <= 0 || d->d <= 0) return RCDM_EINVAL;
-  if ((d->d & 7) || d->d > 160) return RCDM_ESHAPE;
+  // 160 < d <= 512: the wide-head kernel (attn_wide.hip), multiples of 64 only and neither mask
+  const bool wide_head = d->d > 160;
+  if (wide_head ? (d->d > 512 || (d->d & 63) || key_valid || causal) : (d->d & 7) != 0) return RCDM_ESHAPE;
   if ((d->ldq & 7) || (d->ldk & 7) || (d->ldv & 7) || (d->ldo & 3)) return RCDM_ESHAPE;
   // K/V rows of one (batch, head) are addressed with 32-bit byte offsets (raw buffer loads)
   if ((size_t)(d->Lk + 4 * 64) * (size_t)(d->ldk > d->ldv ? d->ldk : d->ldv) * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
+  if (wide_head) {
+    // (so are its Q and O rows)
+    if ((size_t)d->Lq * (size_t)(d->ldq > d->ldo ? d->ldq : d->ldo) * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
+    static int xcd_mode = -1;
+    if (xcd_mode < 0) {
+      const char* e = getenv("RCDM_ATTN_XCD");
+      xcd_mode = e ? atoi(e) : 1;
+    }
+    AttnWideArgs w;
+    w.Q = (const f16*)Q; w.K = (const f16*)K; w.V = (const f16*)V; w.O = (f16*)out;
+    w.batch = d->batch; w.heads = d->heads; w.Lq = d->Lq; w.Lk = d->Lk; w.d = d->d;
+    w.ldq = d->ldq; w.ldk = d->ldk; w.ldv = d->ldv; w.ldo = d->ldo;
+    w.c = d->scale * 1.4426950408889634f;
+    w.plain_order = xcd_mode ? 0 : 1;
+    return rcdm_attn_wide_launch(w, (hipStream_t)stream_);
+  }
   AttnArgs a;
   a.Q = (const f16*)Q; a.K = (const f16*)K; a.V = (const f16*)V; a.O = (f16*)out;
   a.batch = d->batch; a.heads = d->heads; a.Lq = d->Lq; a.Lk = d->Lk; a.d = d->d; a.dch = d->d / 8;

@@ -7,9 +7,12 @@ see oracle/vae_oracle.py).  `AutoencoderKLDecoder` holds the decoder-side parame
 (`post_quant_conv.*`, `decoder.*`), so `load_state_dict(vae_state_dict, strict=False)` takes a real checkpoint, and
 decodes all frames in one batch on the stage-2 kernels: conv3x3 implicit GEMM (nearest-2x upsampling folded into the
 conv's input indexing), per-image GroupNorm(+SiLU), 1x1 shortcuts as GEMMs.  The mid-block attention has ONE head of
-512 channels — too wide for the flash kernel — so it runs as scores = Q K^T (GEMM, scaled in the epilogue), row softmax
-(rcdm_softmax_rows), out = P V (GEMM against V^T, which a GEMM with swapped operands produces directly); the value
-bias is folded into the output projection (softmax rows sum to one).
+512 channels and two forms (mid_attention_form, switch RCDM_VAE_FLASH).  "scores", the default up to 4096 latent pixels
+(512 x 512 images): per image scores = Q K^T (GEMM, scaled in the epilogue), row softmax (rcdm_softmax_rows, rows of
+<= 4096), out = P V (GEMM against V^T, which a GEMM with swapped operands produces directly).  "flash", above: one
+[q | k | v] GEMM and ONE rcdm_flash_attn launch over all images (head dim 512: csrc/attn_wide.hip), no hw x hw buffer,
+so any image size the convolutions take.  In both the value bias is folded into the output projection (softmax rows
+sum to one).
 
 `AutoencoderKL` adds `encoder.*` / `quant_conv.*` and `encode(x).latent_dist` (RCDMs_pipeline.py:429, one call per story on
 the masked source frames): the same kernels, with diffusers' Downsample2D(padding=0) — F.pad (0,1,0,1) then a stride-2
@@ -18,8 +21,9 @@ import torch
 from torch import nn
 
 from . import hip
-from .engine import (CIN_PAD, COUT_PAD, Geo, Packer, Plan, Rows, _NS, emit_conv3x3, emit_gemm, emit_groupnorm,
-                     emit_upsample_conv)
+from . import switches as SW
+from .engine import (CIN_PAD, COUT_PAD, Geo, Packer, Plan, Rows, _NS, emit_conv3x3, emit_flash_attn, emit_gemm,
+                     emit_groupnorm, emit_upsample_conv)
 
 SD15_VAE = dict(block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, out_channels=3,
                 in_channels=3, norm_num_groups=32, scaling_factor=0.18215)
@@ -375,25 +379,62 @@ def _emit_mid_block(plan, pk, m, cur, nxt, geo, groups):
     return nxt
 
 
+SCORES_MAX_TOKENS = 4096    # rcdm_softmax_rows: columns of one row
+FLASH_NARROW_MAX = 160      # rcdm_flash_attn: head dims up to here in steps of 8 ...
+FLASH_WIDE_MAX = 512        # ... and up to here in steps of 64
+
+
+def flash_head_ok(C):
+    """Whether rcdm_flash_attn takes a head of C channels."""
+    return C % 8 == 0 and (C <= FLASH_NARROW_MAX or (C <= FLASH_WIDE_MAX and C % 64 == 0))
+
+
+def mid_attention_form(hw, C, switch=None):
+    """Which form the one-head mid-block attention over hw latent pixels of C channels takes: "scores" (per image Q K^T
+    GEMM -> rcdm_softmax_rows -> P V GEMM through an hw x hw score buffer) or "flash" (one rcdm_flash_attn launch over
+    all images, nothing of size hw^2).  switch: RCDM_VAE_FLASH ("auto" / "1" / "0"; default: the process's setting).
+    Raises NotImplementedError for a size no permitted form covers."""
+    switch = SW.VAE_FLASH if switch is None else str(switch)
+    scores_ok = hw <= SCORES_MAX_TOKENS and hw % 8 == 0
+    if switch == "0" or (switch != "1" and hw <= SCORES_MAX_TOKENS):
+        if not scores_ok:
+            raise NotImplementedError(f"mid-block attention over {hw} tokens: rcdm_softmax_rows holds rows of <= 4096")
+        return "scores"
+    if not flash_head_ok(C):
+        raise NotImplementedError(f"mid-block attention over {hw} tokens of {C} channels: rcdm_flash_attn takes one head of "
+                                  f"<= {FLASH_NARROW_MAX} channels (multiples of 8) or <= {FLASH_WIDE_MAX} (multiples of 64)"
+                                  + ("" if hw > SCORES_MAX_TOKENS else "; unset RCDM_VAE_FLASH for the score-buffer form"))
+    return "flash"
+
+
 def _emit_mid_attention(plan, pk, p, x, geo, out, groups):
     C, n, hw = x.C, geo.n_img, geo.hw
-    if hw > 4096 or hw % 8:
-        raise NotImplementedError(f"mid-block attention over {hw} tokens: rcdm_softmax_rows holds rows of <= 4096")
+    form = mid_attention_form(hw, C)
     a = plan.rows("norm", geo.M, C)
     emit_groupnorm(plan, x, n, hw, pk.vec(p + "group_norm.weight"), pk.vec(p + "group_norm.bias"), 1e-6, False, a, groups)
-    wq, bq = pk.mat_f16(p + "to_q.weight"), pk.vec(p + "to_q.bias")
-    wk, bk = pk.mat_f16(p + "to_k.weight"), pk.vec(p + "to_k.bias")
-    wv = pk.mat_f16(p + "to_v.weight")
     wo = pk.mat_f16(p + "to_out.0.weight")
     # softmax rows sum to one, so P (V0 + 1 bv^T) = P V0 + bv: the value bias moves into the output projection
     bo = (pk.vec(p + "to_out.0.bias") + hip.matmul_f32(pk.f32(p + "to_out.0.weight"), pk.vec(p + "to_v.bias"))).contiguous()
+    ao = plan.rows("vae_ao", geo.M, C, unique=True)
+    if form == "flash":
+        # one [q | k | v] GEMM (N = 3C; any row count), then ONE launch: batch = images, one head of C channels read as
+        # column views of the 3C-wide rows.  No V^T, no score buffer, no per-image loop
+        wqkv = pk.mat_f16(p + "to_q.weight", p + "to_k.weight", p + "to_v.weight")
+        bqkv = torch.cat([pk.vec(p + "to_q.bias"), pk.vec(p + "to_k.bias"), torch.zeros(C, device=plan.device)]).contiguous()
+        qkv = plan.rows("vae_qkv", geo.M, 3 * C, unique=True)
+        emit_gemm(plan, a, wqkv, 3 * C, C, qkv, bias=bqkv)
+        emit_flash_attn(plan, qkv.cols(0, C), qkv.cols(C, C), qkv.cols(2 * C, C), n, 1, hw, hw, C, ao)
+        emit_gemm(plan, ao, wo, C, C, out, bias=bo, residual=x)
+        return
+    wq, bq = pk.mat_f16(p + "to_q.weight"), pk.vec(p + "to_q.bias")
+    wk, bk = pk.mat_f16(p + "to_k.weight"), pk.vec(p + "to_k.bias")
+    wv = pk.mat_f16(p + "to_v.weight")
     q = plan.rows("vae_q", geo.M, C, unique=True)
     k = plan.rows("vae_k", geo.M, C, unique=True)
     emit_gemm(plan, a, wq, C, C, q, bias=bq)
     emit_gemm(plan, a, wk, C, C, k, bias=bk)
     vt = plan.rows("vae_vt", C, hw, unique=True)           # V^T of ONE image: [C][hw]
     sc = plan.rows("vae_scores", hw, hw, unique=True)      # scores / probabilities of one image
-    ao = plan.rows("vae_ao", geo.M, C, unique=True)
     wv_rows = Rows(_Holder16(wv), 0, C, C, C)
     scale = float(C) ** -0.5
     for i in range(n):
