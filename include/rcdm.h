@@ -197,7 +197,9 @@ typedef struct {
   float out_scale;
   int32_t split_k;
   int32_t pad_after_only; /* 0: padding 1 on every side (default).  1: zero rows/columns only AFTER the image —
-                           * diffusers Downsample2D(padding=0): F.pad(x, (0,1,0,1)) then a stride-2 conv (VAE encoder) */
+                           * diffusers Downsample2D(padding=0): F.pad(x, (0,1,0,1)) then a stride-2 conv (VAE encoder).
+                           * Needs stride 2, upsample 0 and EVEN h_in and w_in (h_out = h_in / 2: an odd side would give one
+                           * row less than the symmetric form's formula above); RCDM_ESHAPE otherwise */
   int32_t dup_rows;       /* as rcdm_gemm_desc.dup_rows */
   int32_t c_in2, lda2;    /* rcdm_conv3x3_add1x1 only (0 otherwise): channels and row stride of the second input */
 } rcdm_conv3x3_desc;

@@ -5,7 +5,8 @@ import pytest
 import torch
 
 from oracle import unet_oracle as O
-from tests.test_hip_kernels import DEV, close, h16
+from tests.guard import check_all
+from tests.test_hip_kernels import DEV, close, gin, gout, h16
 
 pytestmark = pytest.mark.gpu
 
@@ -14,15 +15,14 @@ def _run(hip, q, k, v, heads, d, flags=0):
     """q inside a 3C-wide [q|k|v]-style buffer, k | v interleaved in one 2C-wide buffer (as test_flash_attn lays them out)."""
     batch, Lq, C = q.shape
     Lk = k.shape[1]
-    qd = torch.zeros(batch * Lq, 3 * C, dtype=torch.float16)
-    qd[:, :C] = q.reshape(-1, C).half()
-    qd = qd.to(DEV)
-    kv = torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half().to(DEV)
-    out = torch.full((batch * Lq, C), float("nan"), dtype=torch.float16, device=DEV)
-    desc = hip.AttnDesc(batch, heads, Lq, Lk, d, 3 * C, 2 * C, 2 * C, C, d ** -0.5, flags)
+    qd = gin(q.reshape(-1, C).half(), 3 * C)
+    kv = gin(torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half(), 2 * C + 8)
+    out = gout(batch * Lq, C, C + 8)
+    desc = hip.AttnDesc(batch, heads, Lq, Lk, d, 3 * C, 2 * C + 8, 2 * C + 8, C + 8, d ** -0.5, flags)
     hip.flash_attn(desc, qd.data_ptr(), kv.data_ptr(), kv.data_ptr() + 2 * C, out.data_ptr())
     torch.cuda.synchronize()
-    return out.reshape(batch, Lq, C)
+    check_all(out, qd, kv)
+    return out[:, :C].reshape(batch, Lq, C)
 
 
 @pytest.mark.parametrize("batch,heads,Lq,Lk,d", [
@@ -90,8 +90,9 @@ def test_flash_attn_wide_shape_errors(hiplib):
     """Still RCDM_ESHAPE: a masked or causal call above d = 160, d > 512, d % 64 != 0 above 160."""
     from rcdms_amd import hip
     L = 64
-    buf = torch.zeros(L, 3 * 576, dtype=torch.float16, device=DEV)
-    out = torch.zeros(L, 576, dtype=torch.float16, device=DEV)
+    buf = gin(torch.randn(L, 3 * 576, generator=torch.Generator().manual_seed(1)).half())
+    out = gout(L, 512)                           # the one real launch below writes exactly these rows
+    scratch = gout(L, 576)                       # handed to the refused calls only: must stay untouched
     valid = torch.ones(1, L, dtype=torch.uint8, device=DEV)
 
     def desc(d):
@@ -101,16 +102,18 @@ def test_flash_attn_wide_shape_errors(hiplib):
         return buf.data_ptr(), buf.data_ptr() + 2 * d, buf.data_ptr() + 4 * d
 
     with pytest.raises(hip.RcdmError, match="RCDM_ESHAPE"):
-        hip.flash_attn_masked(desc(512), *ptrs(512), valid.data_ptr(), False, out.data_ptr())
+        hip.flash_attn_masked(desc(512), *ptrs(512), valid.data_ptr(), False, scratch.data_ptr())
     with pytest.raises(hip.RcdmError, match="RCDM_ESHAPE"):
-        hip.flash_attn_masked(desc(512), *ptrs(512), 0, True, out.data_ptr())
+        hip.flash_attn_masked(desc(512), *ptrs(512), 0, True, scratch.data_ptr())
     for d in (576, 200):
         with pytest.raises(hip.RcdmError, match="RCDM_ESHAPE"):
-            hip.flash_attn(desc(d), *ptrs(d), out.data_ptr())
+            hip.flash_attn(desc(d), *ptrs(d), scratch.data_ptr())
     # ... and the unmasked entry of the masked symbol is the same call as rcdm_flash_attn
     hip.flash_attn_masked(desc(512), *ptrs(512), 0, False, out.data_ptr())
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
+    check_all(out, scratch, buf)
+    assert torch.isnan(scratch.float()).all(), "a refused call wrote its output"
 
 
 def test_flash_attn_wide_graph_capture(hiplib):
@@ -118,9 +121,9 @@ def test_flash_attn_wide_graph_capture(hiplib):
     from rcdms_amd import hip
     g = torch.Generator().manual_seed(11)
     L, d = 384, 512
-    qkv = (torch.randn(L, 3 * d, generator=g)).half().to(DEV)
-    out_e = torch.zeros(L, d, dtype=torch.float16, device=DEV)
-    out_g = torch.zeros(L, d, dtype=torch.float16, device=DEV)
+    qkv = gin((torch.randn(L, 3 * d, generator=g)).half())
+    out_e = gout(L, d)
+    out_g = gout(L, d)
     desc = hip.AttnDesc(1, 1, L, L, d, 3 * d, 3 * d, 3 * d, d, d ** -0.5)
     hip.flash_attn(desc, qkv.data_ptr(), qkv.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d, out_e.data_ptr())
     torch.cuda.synchronize()
@@ -130,3 +133,4 @@ def test_flash_attn_wide_graph_capture(hiplib):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(out_e, out_g) and out_e.float().abs().max() > 0
+    check_all(out_e, out_g, qkv)

@@ -8,7 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import unet_oracle as O
-from tests.test_hip_kernels import DEV, close, h16, rows_from_5d, rows_to_5d, ws
+from tests.guard import check_all
+from tests.test_hip_kernels import DEV, close, gin, gout, gvec, gw, h16, rows_from_5d, rows_to_5d, ws
 
 pytestmark = pytest.mark.gpu
 
@@ -37,19 +38,20 @@ def test_gemm_random_shapes(hiplib):
         rowvec = torch.randn((M + rps - 1) // rps, Nout, generator=g)
         res = h16(torch.randn(M, Nout, generator=g))
         lda, ldc, ldr = K + 8 * rnd.randint(0, 2), Nout + 8 * rnd.randint(0, 2), Nout + 8 * rnd.randint(0, 2)
-        Ad = torch.zeros(M, lda, dtype=torch.float16); Ad[:, :K] = A.half(); Ad = Ad.to(DEV)
-        Rd = torch.zeros(M, ldr, dtype=torch.float16); Rd[:, :Nout] = res.half(); Rd = Rd.to(DEV)
-        out = torch.full((M, ldc), float("nan"), dtype=torch.float16, device=DEV)
+        ldt = Nout + 8 * random.Random(5000 + case).randint(0, 2)     # (its own stream: the shapes drawn from rnd stay what they were)
+        Ad = gin(A.half(), lda)
+        Rd = gin(res.half(), ldr)
+        out = gout(M, Nout, ldc)
         if geglu:
-            w32, b32 = W.to(DEV), bias.to(DEV)
-            Wd = torch.empty(N, K, dtype=torch.float16, device=DEV)
-            bd = torch.empty(N, dtype=torch.float32, device=DEV)
+            w32, b32 = gin(W), gvec(bias)
+            Wd = gout(N, K)
+            bd = gout(1, N, dtype=torch.float32, guard_rows=1)
             hip.pack_geglu_rows(w32.data_ptr(), b32.data_ptr(), N, K, Wd.data_ptr(), bd.data_ptr())
             hg = F.linear(A, W, bias)
             hid, gate = hg.chunk(2, dim=-1)
             ref = hid * F.gelu(gate)
         else:
-            Wd, bd = W.half().to(DEV), bias.to(DEV)
+            Wd, bd = gw(W), gvec(bias)
             ref = A @ W.t()
             if epi & hip.EPI_BIAS:
                 ref = ref + bias
@@ -60,8 +62,8 @@ def test_gemm_random_shapes(hiplib):
             if epi & hip.EPI_RESIDUAL:
                 ref = ref + res
         ref = ref * scale
-        rvd = rowvec.to(DEV)
-        d = hip.GemmDesc(M, N, K, lda, ldc, ldr, epi, rps, Nout, scale, split)
+        rvd = gin(rowvec, ldt, guard_rows=8)
+        d = hip.GemmDesc(M, N, K, lda, ldc, ldr, epi, rps, ldt, scale, split)
         w = ws(hip.gemm_workspace_bytes(d))
         hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), rvd.data_ptr(), Rd.data_ptr(), out.data_ptr(),
                  w.data_ptr(), w.numel())
@@ -72,6 +74,10 @@ def test_gemm_random_shapes(hiplib):
             raise AssertionError(f"case {case}: M={M} N={N} K={K} epi={epi} split={split} scale={scale:.3f} rps={rps} "
                                  f"lda={lda} ldc={ldc}: {e}")
         assert torch.isnan(out[:, Nout:].float()).all(), f"case {case}: wrote outside the N columns"
+        try:
+            check_all(out, Ad, Rd, Wd, bd, rvd)
+        except AssertionError as e:
+            raise AssertionError(f"case {case}: M={M} N={N} K={K} epi={epi} split={split} lda={lda} ldc={ldc} ldr={ldr} ldt={ldt}: {e}")
 
 
 def test_conv_random_shapes(hiplib):
@@ -93,19 +99,21 @@ def test_conv_random_shapes(hiplib):
         Ho, Wo = ref.shape[-2:]
         lda = cin + 8
         xd = rows_from_5d(x, lda)
-        wp = torch.empty(cout, 9 * cin, dtype=torch.float16, device=DEV)
-        w32 = w.to(DEV)
+        wp = gout(cout, 9 * cin)
+        w32 = gvec(w)
         hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
-        out = torch.empty(n * Ho * Wo, cout, dtype=torch.float16, device=DEV)
-        d = hip.ConvDesc(n, H, W, cin, cout, stride, up, lda, cout, 0, hip.EPI_BIAS, 1, 0, 1.0, rnd.choice([0, 0, 1, 2]))
+        ldc = cout + 8 * random.Random(6000 + case).randint(0, 2)     # (its own stream, as above)
+        out = gout(n * Ho * Wo, cout, ldc)
+        d = hip.ConvDesc(n, H, W, cin, cout, stride, up, lda, ldc, 0, hip.EPI_BIAS, 1, 0, 1.0, rnd.choice([0, 0, 1, 2]))
         wsb = ws(hip.conv3x3_workspace_bytes(d))
-        bd = bias.to(DEV)
+        bd = gvec(bias)
         hip.conv3x3(d, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), wsb.data_ptr(), wsb.numel())
         torch.cuda.synchronize()
         try:
             close(rows_to_5d(out, 1, cout, n, Ho, Wo), ref)
+            check_all(out, wp, xd, w32, bd)
         except AssertionError as e:
-            raise AssertionError(f"case {case}: n={n} {H}x{W} {cin}->{cout} s={stride} up={up}: {e}")
+            raise AssertionError(f"case {case}: n={n} {H}x{W} {cin}->{cout} s={stride} up={up} ldc={ldc}: {e}")
 
 
 def test_flash_random_shapes(hiplib):
@@ -133,10 +141,11 @@ def test_flash_random_shapes(hiplib):
             if causal:
                 mask = mask + torch.full((Lq, Lk), -10000.0).triu_(1)[None]
         ref = O.attention_core(q, k, v, heads, mask=mask)
-        qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
+        ldq, ldk, ldv, ldo = (C + 8 * random.Random(7000 + 4 * case + i).randint(0, 3) for i in range(4))   # (own stream)
+        qd, kd, vd = (gin(t.reshape(-1, C).half(), ld) for t, ld in ((q, ldq), (k, ldk), (v, ldv)))
         vm = valid.to(DEV)
-        out = torch.empty(batch * Lq, C, dtype=torch.float16, device=DEV)
-        desc = hip.AttnDesc(batch, heads, Lq, Lk, d, C, C, C, C, d ** -0.5)
+        out = gout(batch * Lq, C, ldo)
+        desc = hip.AttnDesc(batch, heads, Lq, Lk, d, ldq, ldk, ldv, ldo, d ** -0.5)
         if causal or pad:
             hip.flash_attn_masked(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), vm.data_ptr() if pad else 0, causal,
                                   out.data_ptr())
@@ -144,9 +153,11 @@ def test_flash_random_shapes(hiplib):
             hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
         torch.cuda.synchronize()
         try:
-            close(out.reshape(batch, Lq, C), ref)
+            close(out[:, :C].reshape(batch, Lq, C), ref)
+            check_all(out, qd, kd, vd)
         except AssertionError as e:
-            raise AssertionError(f"case {case}: B={batch} H={heads} Lq={Lq} Lk={Lk} d={d} causal={causal} pad={pad}: {e}")
+            raise AssertionError(f"case {case}: B={batch} H={heads} Lq={Lq} Lk={Lk} d={d} causal={causal} pad={pad} "
+                                 f"ldq={ldq} ldk={ldk} ldv={ldv} ldo={ldo}: {e}")
 
 
 def test_xattn_random_shapes(hiplib):
@@ -167,12 +178,10 @@ def test_xattn_random_shapes(hiplib):
         ldq, ldk, ldv, ldo = (C + 8 * rnd.randint(0, 3) for _ in range(4))
 
         def padded(t, rows, ld):
-            buf = torch.zeros(rows, ld, dtype=torch.float16)
-            buf[:, :C] = t.reshape(rows, C).half()
-            return buf.to(DEV)
+            return gin(t.reshape(rows, C).half(), ld)
         qd, kd, vd = padded(q, batch * Lq, ldq), padded(k, batch * Lk, ldk), padded(v, batch * Lk, ldv)
-        img = torch.empty(hip.xattn_image_bytes(batch, heads, d), dtype=torch.uint8, device=DEV)
-        out = torch.full((batch * Lq, ldo), float("nan"), dtype=torch.float16, device=DEV)
+        img = gout(1, hip.xattn_image_bytes(batch, heads, d), dtype=torch.uint8, guard_rows=1)
+        out = gout(batch * Lq, C, ldo)
         desc = hip.AttnDesc(batch, heads, Lq, Lk, d, ldq, ldk, ldv, ldo, d ** -0.5)
         hip.xattn_pack_kv(kd.data_ptr(), vd.data_ptr(), batch, Lk, heads, d, ldk, ldv, img.data_ptr())
         hip.xattn(desc, qd.data_ptr(), img.data_ptr(), out.data_ptr())
@@ -180,6 +189,7 @@ def test_xattn_random_shapes(hiplib):
         try:
             close(out[:, :C].reshape(batch, Lq, C), ref)
             assert torch.isnan(out[:, C:].float()).all(), "wrote outside the C columns"
+            check_all(out, img, qd, kd, vd)
         except AssertionError as e:
             raise AssertionError(f"case {case}: B={batch} H={heads} Lq={Lq} Lk={Lk} d={d}: {e}")
 
@@ -202,14 +212,15 @@ def test_layernorm_random_shapes(hiplib):
         if pe:
             ref = ref + table[(torch.arange(M) // rpf) % frames]
         ldx, ldy = C + 8 * rnd.randint(0, 2), C + 8 * rnd.randint(0, 2)
-        xd = torch.zeros(M, ldx, dtype=torch.float16); xd[:, :C] = x.half(); xd = xd.to(DEV)
-        y = torch.full((M, ldy), float("nan"), dtype=torch.float16, device=DEV)
-        gd, bd, td = gamma.to(DEV), beta.to(DEV), table.to(DEV)
+        xd = gin(x.half(), ldx)
+        y = gout(M, C, ldy)
+        gd, bd, td = gvec(gamma), gvec(beta), gvec(table)
         d = hip.LayerNormDesc(M, C, ldx, ldy, 1e-5, rpf, frames)
         hip.layernorm(d, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), td.data_ptr() if pe else 0, y.data_ptr())
         torch.cuda.synchronize()
         try:
             close(y[:, :C], ref)
             assert torch.isnan(y[:, C:].float()).all(), "wrote outside the C columns"
+            check_all(y, xd, gd, bd, td)
         except AssertionError as e:
             raise AssertionError(f"case {case}: M={M} C={C} pe={pe} frames={frames} rpf={rpf}: {e}")

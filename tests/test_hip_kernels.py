@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import unet_oracle as O
+from tests.guard import check_all, check_out, check_written, guarded_in, guarded_out, guarded_vec, guarded_w
 
 pytestmark = pytest.mark.gpu
 
@@ -32,14 +33,31 @@ def h16(x):
     return x.half().float()
 
 
+def gin(t, ld=None, guard_rows=256):
+    """A read-only 2-D operand inside poison (tests/guard.py): pad columns and guard rows above and below."""
+    return guarded_in(t, ld, device=DEV, guard_rows=guard_rows)[0]
+
+
+def gout(rows, C, ld=None, dtype=torch.float16, guard_rows=256):
+    """A NaN-filled output with pad columns and guard rows above and below."""
+    return guarded_out(rows, C, ld, dtype, device=DEV, guard_rows=guard_rows)[0]
+
+
+def gvec(v):
+    """A dense fp32 vector / table operand at a 16-byte-aligned offset inside poison."""
+    return guarded_vec(v.float(), device=DEV)[0]
+
+
+def gw(W):
+    """A dense f16 weight matrix W[N][K] with poisoned guard rows around it."""
+    return guarded_w(W.half(), device=DEV)[0]
+
+
 def rows_from_5d(x5, ld=None, dev=DEV):
-    """(b,C,f,H,W) fp32 -> f16 rows [b*f*H*W][ld] on the GPU."""
+    """(b,C,f,H,W) fp32 -> f16 rows [b*f*H*W][ld] on the GPU, the pad columns and guard rows around them poisoned."""
     b, c, f, h, w = x5.shape
     r = x5.permute(0, 2, 3, 4, 1).reshape(b * f * h * w, c).half()
-    ld = ld or c
-    out = torch.zeros(r.shape[0], ld, dtype=torch.float16)
-    out[:, :c] = r
-    return out.to(dev)
+    return guarded_in(r, ld or c, device=dev)[0]
 
 
 def rows_to_5d(rows, b, c, f, h, w):
@@ -80,12 +98,11 @@ def test_gemm(hiplib, M, N, K, epi, split, variant):
         ref = ref + rowvec[torch.arange(M) // rps]
     if epi & 4:
         ref = ref + res
-    lda, ldc, ldr = K + 8, N + 16, N + 8
-    Ad = torch.zeros(M, lda, dtype=torch.float16); Ad[:, :K] = A.half(); Ad = Ad.to(DEV)
-    Rd = torch.zeros(M, ldr, dtype=torch.float16); Rd[:, :N] = res.half(); Rd = Rd.to(DEV)
-    Wd, bd, rvd = W.half().to(DEV), bias.to(DEV), rowvec.to(DEV)
-    out = torch.full((M, ldc), float("nan"), dtype=torch.float16, device=DEV)
-    d = hip.GemmDesc(M, N, K, lda, ldc, ldr, epi, rps, N, 1.0, split)
+    lda, ldc, ldr, ldt = K + 8, N + 16, N + 8, N + 8
+    Ad, Rd = gin(A.half(), lda), gin(res.half(), ldr)
+    Wd, bd, rvd = gw(W), gvec(bias), gin(rowvec, ldt, guard_rows=8)
+    out = gout(M, N, ldc)
+    d = hip.GemmDesc(M, N, K, lda, ldc, ldr, epi, rps, ldt, 1.0, split)
     w = ws(hip.gemm_workspace_bytes(d))
     hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), rvd.data_ptr(), Rd.data_ptr(), out.data_ptr(),
              w.data_ptr(), w.numel())
@@ -93,6 +110,7 @@ def test_gemm(hiplib, M, N, K, epi, split, variant):
     hip.set_igemm_variant(-1)
     close(out[:, :N], ref)
     assert torch.isnan(out[:, N:].float()).all(), "wrote outside the N columns"
+    check_all(out, Ad, Rd, Wd, bd, rvd)
 
 
 def test_gemm_transpose_detecting(hiplib):
@@ -102,12 +120,13 @@ def test_gemm_transpose_detecting(hiplib):
     A = torch.eye(M, K)
     W = (torch.arange(N)[:, None] * 0.01 + torch.arange(K)[None, :] * 0.37) % 3.0
     W = h16(W)
-    out = torch.empty(M, N, dtype=torch.float16, device=DEV)
+    out = gout(M, N)
     d = hip.GemmDesc(M, N, K, K, N, N, 0, 1, 0, 1.0, 1)
-    Ad, Wd = A.half().to(DEV), W.half().to(DEV)
+    Ad, Wd = gin(A.half()), gw(W)
     hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), 0, 0, 0, out.data_ptr(), 0, 0)
     torch.cuda.synchronize()
     close(out, W.t(), rel=1e-3, abs_frac=1e-3)
+    check_all(out, Ad, Wd)
 
 
 @pytest.mark.parametrize("variant", [6, 7, 8, 9])
@@ -140,9 +159,9 @@ def test_gemm_pingpong(hiplib, M, N, K, epi, split, variant):
         ref = F.gelu(ref)
     if epi & 4:
         ref = ref + res
-    Ad, Wd, Rd = A.half().to(DEV), W.half().to(DEV), res.half().to(DEV)
-    bd, rvd = bias.to(DEV), rowvec.to(DEV)
-    out = torch.full((M, N + 8), float("nan"), dtype=torch.float16, device=DEV)
+    Ad, Wd, Rd = gin(A.half()), gw(W), gin(res.half())
+    bd, rvd = gvec(bias), gvec(rowvec)
+    out = gout(M, N, N + 8)
     d = hip.GemmDesc(M, N, K, K, N + 8, N, epi, rps, N, 1.0, split)
     w = ws(hip.gemm_workspace_bytes(d))
     for _ in range(2):   # twice: a stale-LDS or missed-wait race rarely shows on a cold first launch only
@@ -152,6 +171,7 @@ def test_gemm_pingpong(hiplib, M, N, K, epi, split, variant):
     hip.set_igemm_variant(-1)
     close(out[:, :N], ref)
     assert torch.isnan(out[:, N:].float()).all(), "wrote outside the N columns"
+    check_all(out, Ad, Wd, Rd, bd, rvd)
 
 
 @pytest.mark.parametrize("M,N,K,epi,pe,dup", [
@@ -181,11 +201,11 @@ def test_gemm_ln(hiplib, M, N, K, epi, pe, dup):
     y_ref = F.layer_norm(h16(x_ref), (N,), gamma, beta, 1e-5)
     if pe:
         y_ref = y_ref + table[(torch.arange(M) // rpf) % frames]
-    Ad, Wd, Rd = A.half().to(DEV), W.half().to(DEV), res.half().to(DEV)
-    bd, gd, btd, td = bias.to(DEV), gamma.to(DEV), beta.to(DEV), table.to(DEV)
+    Ad, Wd, Rd = gin(A.half()), gw(W), gin(res.half())
+    bd, gd, btd, td = gvec(bias), gvec(gamma), gvec(beta), gvec(table)
     rows = M + (dup if dup else 0)
-    out = torch.full((rows, N + 8), float("nan"), dtype=torch.float16, device=DEV)
-    y = torch.full((M, N + 8), float("nan"), dtype=torch.float16, device=DEV)
+    out = gout(rows, N, N + 8)
+    y = gout(M, N, N + 8)
     d = hip.GemmDesc(M, N, K, K, N + 8, N, epi, 1, 0, 1.0, 1, dup)
     ln = hip.LnFuse(gd.data_ptr(), btd.data_ptr(), td.data_ptr() if pe else 0, y.data_ptr(), N + 8, rpf, frames, 1e-5)
     for _ in range(2):
@@ -196,10 +216,11 @@ def test_gemm_ln(hiplib, M, N, K, epi, pe, dup):
     assert torch.isnan(out[:, N:].float()).all() and torch.isnan(y[:, N:].float()).all(), "wrote outside the N columns"
     if dup:
         assert torch.equal(out[dup:dup + M, :N], out[:M, :N])
+    check_all(out, y, Ad, Wd, Rd, bd, gd, btd, td)
     # the unfused pair: same GEMM kernel (variant 6 = the 160x320 ping-pong tile), then rcdm_layernorm on its output
     hip.set_igemm_variant(6)
-    out2 = torch.empty(M, N, dtype=torch.float16, device=DEV)
-    y2 = torch.empty(M, N, dtype=torch.float16, device=DEV)
+    out2 = gout(M, N)
+    y2 = gout(M, N)
     d2 = hip.GemmDesc(M, N, K, K, N, N, epi, 1, 0, 1.0, 1, 0)
     w = ws(hip.gemm_workspace_bytes(d2))
     hip.gemm(d2, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), 0, Rd.data_ptr(), out2.data_ptr(), w.data_ptr(), w.numel())
@@ -210,6 +231,7 @@ def test_gemm_ln(hiplib, M, N, K, epi, pe, dup):
     assert torch.equal(out[:M, :N], out2), "fused GEMM output differs from the unfused kernel's"
     dy = (y[:, :N].float() - y2.float()).abs().max().item()
     assert dy <= 2e-3 * y_ref.abs().max().item(), dy          # same inputs, another summation order in the row statistics
+    check_all(out2, y2, Ad, Wd, Rd, bd, gd, btd, td)
 
 
 def test_gemm_ln_rejects(hiplib):
@@ -234,8 +256,8 @@ def test_gemm_dup_rows(hiplib, variant, split):
     M, N, K = 300, 320, 256
     A = h16(torch.randn(M, K, generator=g)); W = h16(torch.randn(N, K, generator=g) * K ** -0.5)
     bias = torch.randn(N, generator=g)
-    Ad, Wd, bd = A.half().to(DEV), W.half().to(DEV), bias.to(DEV)
-    out = torch.full((2 * M + 3, N), float("nan"), dtype=torch.float16, device=DEV)
+    Ad, Wd, bd = gin(A.half()), gw(W), gvec(bias)
+    out = gout(2 * M + 3, N)
     d = hip.GemmDesc(M, N, K, K, N, 0, 1, 1, 0, 1.0, split, M + 3)
     w = ws(hip.gemm_workspace_bytes(d))
     hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), w.data_ptr(), w.numel())
@@ -243,6 +265,7 @@ def test_gemm_dup_rows(hiplib, variant, split):
     hip.set_igemm_variant(-1)
     close(out[:M], A @ W.t() + bias)
     assert torch.equal(out[:M], out[M + 3:]) and torch.isnan(out[M:M + 3].float()).all()
+    check_all(out, Ad, Wd, bd)
 
 
 @pytest.mark.parametrize("variant", [6, 7, 8])
@@ -253,24 +276,36 @@ def test_gemm_pingpong_bitwise_vs_128(hiplib, variant):
     from rcdms_amd import hip
     g = torch.Generator().manual_seed(77)
     M, N, K = 1600, 960, 1280
-    Ad = h16(torch.randn(M, K, generator=g)).half().to(DEV)
-    Wd = h16(torch.randn(N, K, generator=g) * K ** -0.5).half().to(DEV)
+    Ad = gin(h16(torch.randn(M, K, generator=g)).half())
+    Wd = gw(h16(torch.randn(N, K, generator=g) * K ** -0.5))
     d = hip.GemmDesc(M, N, K, K, N, 0, 0, 1, 0, 1.0, 1)
     outs = []
     for v in (variant, variant, variant, 1):
         hip.set_igemm_variant(v)
-        o = torch.empty(M, N, dtype=torch.float16, device=DEV)
+        o = gout(M, N)
         hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), 0, 0, 0, o.data_ptr(), 0, 0)
         torch.cuda.synchronize()
         outs.append(o)
     hip.set_igemm_variant(-1)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), "ping-pong kernel is not deterministic"
     close(outs[0], outs[3].float(), rel=2e-3, abs_frac=1e-3)
+    check_all(*outs, Ad, Wd)
 
 
 @pytest.mark.parametrize("variant", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
 @pytest.mark.parametrize("split", [1, 2])
 def test_gemm_geglu(hiplib, split, variant):
+    _gemm_geglu(split, variant, 8)
+
+
+@pytest.mark.parametrize("variant", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
+@pytest.mark.parametrize("split", [1, 2])
+def test_gemm_geglu_dense(hiplib, split, variant):
+    _gemm_geglu(split, variant, 0)
+
+
+def _gemm_geglu(split, variant, pad):
+    """pad: lda = K + pad, ldc = N / 2 + pad (the GEGLU output is half as wide as the GEMM)."""
     from rcdms_amd import hip
     hip.set_igemm_variant(variant)
     g = torch.Generator().manual_seed(7)
@@ -281,17 +316,18 @@ def test_gemm_geglu(hiplib, split, variant):
     hg = F.linear(x, sd["ff.net.0.proj.weight"], sd["ff.net.0.proj.bias"])
     hidden, gate = hg.chunk(2, dim=-1)
     ref = hidden * F.gelu(gate)
-    wp = torch.empty(8 * C, C, dtype=torch.float16, device=DEV)
-    bp = torch.empty(8 * C, dtype=torch.float32, device=DEV)
-    w32, b32, xd = sd["ff.net.0.proj.weight"].to(DEV), sd["ff.net.0.proj.bias"].to(DEV), x.half().to(DEV)
+    wp = gout(8 * C, C)
+    bp = gout(1, 8 * C, dtype=torch.float32, guard_rows=1)
+    w32, b32, xd = gin(sd["ff.net.0.proj.weight"]), gvec(sd["ff.net.0.proj.bias"]), gin(x.half(), C + pad)
     hip.pack_geglu_rows(w32.data_ptr(), b32.data_ptr(), 8 * C, C, wp.data_ptr(), bp.data_ptr())
-    out = torch.empty(M, 4 * C, dtype=torch.float16, device=DEV)
-    d = hip.GemmDesc(M, 8 * C, C, C, 4 * C, 0, hip.EPI_BIAS | hip.EPI_GEGLU, 1, 0, 1.0, split)
+    out = gout(M, 4 * C, 4 * C + pad)
+    d = hip.GemmDesc(M, 8 * C, C, C + pad, 4 * C + pad, 0, hip.EPI_BIAS | hip.EPI_GEGLU, 1, 0, 1.0, split)
     w = ws(hip.gemm_workspace_bytes(d))
     hip.gemm(d, xd.data_ptr(), wp.data_ptr(), bp.data_ptr(), 0, 0, out.data_ptr(), w.data_ptr(), w.numel())
     torch.cuda.synchronize()
     hip.set_igemm_variant(-1)
-    close(out, ref)
+    close(out[:, :4 * C], ref)
+    check_all(out, wp, bp, w32, b32, xd)
 
 
 @pytest.mark.parametrize("b,f,H,W,cin,cout,stride,up,split", [
@@ -319,19 +355,20 @@ def test_conv3x3(hiplib, b, f, H, W, cin, cout, stride, up, split, variant):
     lda = cin + 8
     xd = rows_from_5d(x, lda)
     rd = rows_from_5d(res)
-    wp = torch.empty(cout, 9 * cin, dtype=torch.float16, device=DEV)
-    w32 = w.to(DEV)
+    wp = gout(cout, 9 * cin)
+    w32 = gvec(w)
     hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
-    out = torch.empty(b * f * Ho * Wo, cout, dtype=torch.float16, device=DEV)
+    out = gout(b * f * Ho * Wo, cout)
     d = hip.ConvDesc(b * f, H, W, cin, cout, stride, up, lda, cout, cout,
                      hip.EPI_BIAS | hip.EPI_ROWVEC | hip.EPI_RESIDUAL, f * Ho * Wo, cout, 1.0, split)
     wsb = ws(hip.conv3x3_workspace_bytes(d))
-    bd, td = bias.to(DEV), temb.to(DEV)
+    bd, td = gvec(bias), gvec(temb)
     hip.conv3x3(d, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), td.data_ptr(), rd.data_ptr(), out.data_ptr(),
                 wsb.data_ptr(), wsb.numel())
     torch.cuda.synchronize()
     hip.set_igemm_variant(-1)
     close(rows_to_5d(out, b, cout, f, Ho, Wo), ref)
+    check_all(out, wp, xd, rd, w32, bd, td)
 
 
 @pytest.mark.parametrize("b,f,H,W,cin,cin2,cout,split", [
@@ -362,14 +399,14 @@ def test_conv3x3_add1x1(hiplib, b, f, H, W, cin, cin2, cout, split, variant):
            + temb[:, :, None, None, None] + res) * 0.5
     lda, lda2 = cin + 8, cin2 + 16
     xd, x2d, rd = rows_from_5d(x, lda), rows_from_5d(x2, lda2), rows_from_5d(res)
-    wp = torch.empty(cout, 9 * cin, dtype=torch.float16, device=DEV)
-    w32 = w.to(DEV)
+    wp = gout(cout, 9 * cin)
+    w32 = gvec(w)
     hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
-    wk = torch.cat([wp, w2.half().to(DEV)], dim=1).contiguous()
-    out = torch.full((b * f * H * W, cout), float("nan"), dtype=torch.float16, device=DEV)
+    wk = gw(torch.cat([wp, w2.half().to(DEV)], dim=1))
+    out = gout(b * f * H * W, cout)
     d = hip.ConvDesc(b * f, H, W, cin, cout, 1, 0, lda, cout, cout, hip.EPI_BIAS | hip.EPI_ROWVEC | hip.EPI_RESIDUAL,
                      f * H * W, cout, 0.5, split, 0, 0, cin2, lda2)
-    bd, td = bias.to(DEV), temb.to(DEV)
+    bd, td = gvec(bias), gvec(temb)
     hip.set_igemm_variant(variant)
     try:
         wsb = ws(hip.conv3x3_workspace_bytes(d))
@@ -383,6 +420,7 @@ def test_conv3x3_add1x1(hiplib, b, f, H, W, cin, cin2, cout, split, variant):
     finally:
         hip.set_igemm_variant(-1)
     close(rows_to_5d(out, b, cout, f, H, W), ref)
+    check_all(out, wp, xd, x2d, rd, wk, w32, bd, td)
 
 
 def test_conv3x3_add1x1_refusals(hiplib):
@@ -423,8 +461,9 @@ def test_conv3x3_upsample_phase_form(hiplib, n_img, H, W, cin, cout, variant, sp
     ref = O.conv_frames(F.interpolate(x, scale_factor=[1.0, 2.0, 2.0], mode="nearest"), w, bias, stride=1, padding=1)
     lda = cin + 8
     xd = rows_from_5d(x, lda)
-    w32, bd = w.to(DEV), bias.to(DEV)
-    wp2 = torch.empty(4, cout, 4 * cin, dtype=torch.float16, device=DEV)
+    w32, bd = gvec(w), gvec(bias)
+    wp2_h = gout(4 * cout, 4 * cin)
+    wp2 = wp2_h.view(4, cout, 4 * cin)
     hip.pack_conv3x3_up2(w32.data_ptr(), cout, cin, wp2.data_ptr())
     # the packed image against the definition: phase (a, b), source tap (r, c) = sum of the 3x3 taps that land on it
     rows = {0: ([0], [1, 2]), 1: ([0, 1], [2])}
@@ -435,7 +474,7 @@ def test_conv3x3_upsample_phase_form(hiplib, n_img, H, W, cin, cout, variant, sp
                     want = w[:, :, rows[a][r]][:, :, :, rows[b][c]].sum(dim=(2, 3))
                     got = wp2[2 * a + b].view(cout, 4, cin)[:, 2 * r + c].float().cpu()
                     assert (got - want).abs().max() <= 1e-3 * want.abs().max() + 1e-6
-    out = torch.full((n_img * 4 * H * W, cout), float("nan"), dtype=torch.float16, device=DEV)
+    out = gout(n_img * 4 * H * W, cout)
     d2 = hip.ConvDesc(n_img, H, W, cin, cout, 1, 2, lda, cout, 0, hip.EPI_BIAS, 1, 0, 1.0, split)
     hip.set_igemm_variant(variant)
     try:
@@ -447,15 +486,17 @@ def test_conv3x3_upsample_phase_form(hiplib, n_img, H, W, cin, cout, variant, sp
     finally:
         hip.set_igemm_variant(-1)
     close(rows_to_5d(out, 1, cout, n_img, 2 * H, 2 * W), ref)
-    wp = torch.empty(cout, 9 * cin, dtype=torch.float16, device=DEV)
+    wp = gout(cout, 9 * cin)
     hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
-    out1 = torch.empty_like(out)
+    out1 = gout(n_img * 4 * H * W, cout)
     d1 = hip.ConvDesc(n_img, H, W, cin, cout, 1, 1, lda, cout, 0, hip.EPI_BIAS, 1, 0, 1.0, 0)
     wsb = ws(hip.conv3x3_workspace_bytes(d1))
     hip.conv3x3(d1, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, 0, out1.data_ptr(), wsb.data_ptr(), wsb.numel())
     torch.cuda.synchronize()
     diff = (out.float() - out1.float()).abs().max().item()
     assert diff <= 4e-3 * ref.abs().max().item(), diff
+    check_all(out, out1, wp, xd, w32, bd)
+    check_out(wp2_h)
 
 
 def test_shape_rules_override_the_tile_choice(hiplib):
@@ -467,16 +508,17 @@ def test_shape_rules_override_the_tile_choice(hiplib):
     A = h16(torch.randn(M, K, generator=g))
     W = h16(torch.randn(N, K, generator=g) * K ** -0.5)
     ref = A @ W.t()
-    Ad, Wd = A.half().to(DEV), W.half().to(DEV)
+    Ad, Wd = gin(A.half()), gw(W)
     d = hip.GemmDesc(M, N, K, K, N, 0, 0, 1, 0, 1.0, 0)
     other = hip.GemmDesc(M, N, 4096, 4096, N, 0, 0, 1, 0, 1.0, 0)   # (a shape the library's own table has no rule for)
 
     def run():
         w = ws(hip.gemm_workspace_bytes(d))
-        out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
+        out = gout(M, N)
         hip.gemm(d, Ad.data_ptr(), Wd.data_ptr(), 0, 0, 0, out.data_ptr(), w.data_ptr(), w.numel())
         torch.cuda.synchronize()
         close(out, ref)
+        check_all(out, Ad, Wd)
     try:
         hip.set_shape_rules("off")
         base, base_other = hip.gemm_workspace_bytes(d), hip.gemm_workspace_bytes(other)
@@ -555,14 +597,15 @@ def test_groupnorm(hiplib, b, f, H, W, C, cross, silu):
         ref = F.silu(ref)
     ldx = C + 8
     xd = rows_from_5d(x, ldx)
-    y = torch.empty(b * f * H * W, C, dtype=torch.float16, device=DEV)
+    y = gout(b * f * H * W, C)
     samples, rps = (b, f * H * W) if cross else (b * f, H * W)
     d = hip.GroupNormDesc(samples, rps, C, 32, ldx, C, eps, int(silu))
     w = ws(hip.groupnorm_workspace_bytes(d))
-    gd, bd = gamma.to(DEV), beta.to(DEV)
+    gd, bd = gvec(gamma), gvec(beta)
     hip.groupnorm_silu(d, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), y.data_ptr(), w.data_ptr(), w.numel())
     torch.cuda.synchronize()
     close(rows_to_5d(y, b, C, f, H, W), ref)
+    check_all(y, xd, gd, bd)
 
 
 @pytest.mark.parametrize("kind,b,f,H,W,cin,cout,cross,split,variant", [
@@ -585,19 +628,19 @@ def test_splitk_gnstat_is_bit_identical(hiplib, kind, b, f, H, W, cin, cout, cro
     hip.set_igemm_variant(variant)
     g = torch.Generator().manual_seed(31 + cin + cout + split)
     n_img, M = b * f, b * f * H * W
-    bias = torch.randn(cout, generator=g).to(DEV)
-    rv = torch.randn(b, cout, generator=g).to(DEV)                       # per-sample row vector (time_emb_proj rows)
-    res = h16(torch.randn(M, cout, generator=g)).half().to(DEV)
-    gamma, beta = torch.randn(cout, generator=g).to(DEV), torch.randn(cout, generator=g).to(DEV)
+    bias = gvec(torch.randn(cout, generator=g))
+    rv = gvec(torch.randn(b, cout, generator=g))                         # per-sample row vector (time_emb_proj rows)
+    res = gin(h16(torch.randn(M, cout, generator=g)).half())
+    gamma, beta = gvec(torch.randn(cout, generator=g)), gvec(torch.randn(cout, generator=g))
     samples, rps = (b, f * H * W) if cross else (n_img, H * W)
     ldc = cout + 8
     gnd = hip.GroupNormDesc(samples, rps, cout, 32, ldc, cout, 1e-5 if cross else 1e-6, int(cross))
     epi = 1 | 2 | 4
     if kind == "conv+1x1":
         cin2 = 192
-        x = h16(torch.randn(M, cin, generator=g)).half().to(DEV)
-        x2 = h16(torch.randn(M, cin2, generator=g)).half().to(DEV)
-        w = h16(torch.randn(cout, 9 * cin + cin2, generator=g) * (9 * cin) ** -0.5).half().to(DEV)
+        x = gin(h16(torch.randn(M, cin, generator=g)).half())
+        x2 = gin(h16(torch.randn(M, cin2, generator=g)).half())
+        w = gw(h16(torch.randn(cout, 9 * cin + cin2, generator=g) * (9 * cin) ** -0.5))
         d = hip.ConvDesc(n_img, H, W, cin, cout, 1, 0, cin, ldc, cout, epi, f * H * W, cout, 1.0, split, 0, 0, cin2, cin2)
         wsb = hip.conv3x3_workspace_bytes(d)
         ok = hip.conv3x3_gnstat_ok(d, gnd)
@@ -606,8 +649,8 @@ def test_splitk_gnstat_is_bit_identical(hiplib, kind, b, f, H, W, cin, cout, cro
         fused = lambda o, k, gk: hip.conv3x3_add1x1_gnstat(d, gnd, x.data_ptr(), x2.data_ptr(), w.data_ptr(), bias.data_ptr(), rv.data_ptr(),
                                                           res.data_ptr(), o.data_ptr(), k.data_ptr(), k.numel(), gk.data_ptr(), gk.numel())
     elif kind == "conv":
-        x = h16(torch.randn(M, cin, generator=g)).half().to(DEV)
-        w = h16(torch.randn(cout, 9 * cin, generator=g) * (9 * cin) ** -0.5).half().to(DEV)
+        x = gin(h16(torch.randn(M, cin, generator=g)).half())
+        w = gw(h16(torch.randn(cout, 9 * cin, generator=g) * (9 * cin) ** -0.5))
         d = hip.ConvDesc(n_img, H, W, cin, cout, 1, 0, cin, ldc, cout, epi, f * H * W, cout, 1.0, split, 0, 0)
         wsb = hip.conv3x3_workspace_bytes(d)
         ok = hip.conv3x3_gnstat_ok(d, gnd)
@@ -615,8 +658,8 @@ def test_splitk_gnstat_is_bit_identical(hiplib, kind, b, f, H, W, cin, cout, cro
         fused = lambda o, k, gk: hip.conv3x3_gnstat(d, gnd, x.data_ptr(), w.data_ptr(), bias.data_ptr(), rv.data_ptr(), res.data_ptr(), o.data_ptr(),
                                                    k.data_ptr(), k.numel(), gk.data_ptr(), gk.numel())
     else:
-        x = h16(torch.randn(M, cin, generator=g)).half().to(DEV)
-        w = h16(torch.randn(cout, cin, generator=g) * cin ** -0.5).half().to(DEV)
+        x = gin(h16(torch.randn(M, cin, generator=g)).half())
+        w = gw(h16(torch.randn(cout, cin, generator=g) * cin ** -0.5))
         d = hip.GemmDesc(M, cout, cin, cin, ldc, cout, epi, f * H * W, cout, 1.0, split, 0)
         wsb = hip.gemm_workspace_bytes(d)
         ok = hip.gemm_gnstat_ok(d, gnd)
@@ -626,8 +669,8 @@ def test_splitk_gnstat_is_bit_identical(hiplib, kind, b, f, H, W, cin, cout, cro
     assert wsb > 0 and ok and hip.groupnorm_prestat_ok(gnd)
     outs = []
     for mode in ("separate", "fused"):
-        o = torch.full((M, ldc), float("nan"), dtype=torch.float16, device=DEV)
-        y = torch.full((M, cout), float("nan"), dtype=torch.float16, device=DEV)
+        o = gout(M, cout, ldc)
+        y = gout(M, cout)
         k, gk = ws(wsb), ws(hip.groupnorm_workspace_bytes(gnd))
         if mode == "separate":
             plain(o, k)
@@ -638,6 +681,8 @@ def test_splitk_gnstat_is_bit_identical(hiplib, kind, b, f, H, W, cin, cout, cro
         torch.cuda.synchronize()
         outs.append((o[:, :cout].clone(), y.clone()))
         assert torch.isnan(o[:, cout:].float()).all(), "wrote outside the output columns"
+        check_all(o, y, x, w, bias, rv, res, gamma, beta)
+        check_written(o), check_written(y)       # names the rows a skipped tile or slab left unwritten
     hip.set_igemm_variant(-1)
     assert torch.equal(outs[0][0], outs[1][0]), "the producer's rows differ"
     assert torch.equal(outs[0][1], outs[1][1]), "the norm's output differs"
@@ -681,20 +726,22 @@ def test_groupnorm_fold_is_bit_identical(hiplib, b, f, H, W, C):
     from rcdms_amd import hip
     g = torch.Generator().manual_seed(21 + C)
     x = h16(torch.randn(b * f * H * W, C, generator=g) * 3.0 + 1.5)
-    gamma, beta = torch.randn(C, generator=g).to(DEV), torch.randn(C, generator=g).to(DEV)
-    xd = x.half().to(DEV)
+    gamma, beta = gvec(torch.randn(C, generator=g)), gvec(torch.randn(C, generator=g))
+    xd = gin(x.half())
     d = hip.GroupNormDesc(b * f, H * W, C, 32, C, C, 1e-6, 0)
     w = ws(hip.groupnorm_workspace_bytes(d))
     outs = []
     for mode in (0, 1):
         hip.set_groupnorm_fold(mode)
-        y = torch.full((b * f * H * W, C), float("nan"), dtype=torch.float16, device=DEV)
+        y = gout(b * f * H * W, C)
         hip.groupnorm_silu(d, xd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), w.data_ptr(), w.numel())
         torch.cuda.synchronize()
         outs.append(y)
     hip.set_groupnorm_fold(-1)
     assert torch.isfinite(outs[1].float()).all()
     assert torch.equal(outs[0], outs[1])
+    check_all(*outs, xd, gamma, beta)
+    check_written(outs[0]), check_written(outs[1])
 
 
 @pytest.mark.parametrize("M,C,pe", [(50, 320, False), (40, 640, True), (7, 1280, True), (33, 64, False),
@@ -718,13 +765,14 @@ def test_layernorm(hiplib, M, C, pe):
     table = O.sinusoid_table(C, frames)
     if pe:
         ref = ref + table[(torch.arange(M) // rpf) % frames]
-    xd = x.half().to(DEV)
-    y = torch.empty(M, C, dtype=torch.float16, device=DEV)
+    xd = gin(x.half())
+    y = gout(M, C)
     d = hip.LayerNormDesc(M, C, C, C, 1e-5, rpf, frames)
-    gd, bd, td = gamma.to(DEV), beta.to(DEV), table.to(DEV)
+    gd, bd, td = gvec(gamma), gvec(beta), gvec(table)
     hip.layernorm(d, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), td.data_ptr() if pe else 0, y.data_ptr())
     torch.cuda.synchronize()
     close(y, ref)
+    check_all(y, xd, gd, bd, td)
 
 
 @pytest.mark.parametrize("batch,heads,Lq,Lk,d", [
@@ -746,13 +794,14 @@ def test_flash_attn(hiplib, batch, heads, Lq, Lk, d):
     v = h16(torch.randn(batch, Lk, C, generator=g))
     ref = O.attention_core(q, k, v, heads)
     # q inside a fused [q|k|v]-style wider buffer, k/v interleaved in one [k|v] buffer
-    qd = torch.zeros(batch * Lq, 3 * C, dtype=torch.float16); qd[:, :C] = q.reshape(-1, C).half(); qd = qd.to(DEV)
-    kv = torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half().to(DEV)
-    out = torch.empty(batch * Lq, C, dtype=torch.float16, device=DEV)
+    qd = gin(q.reshape(-1, C).half(), 3 * C)
+    kv = gin(torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half())
+    out = gout(batch * Lq, C)
     desc = hip.AttnDesc(batch, heads, Lq, Lk, d, 3 * C, 2 * C, 2 * C, C, d ** -0.5)
     hip.flash_attn(desc, qd.data_ptr(), kv.data_ptr(), kv.data_ptr() + 2 * C, out.data_ptr())
     torch.cuda.synchronize()
     close(out.reshape(batch, Lq, C), ref)
+    check_all(out, qd, kv)
 
 
 @pytest.mark.parametrize("batch,heads,Lq,Lk,d", [
@@ -775,11 +824,11 @@ def test_xattn_short_keys(hiplib, batch, heads, Lq, Lk, d):
     k = h16(torch.randn(batch, Lk, C, generator=g))
     v = h16(torch.randn(batch, Lk, C, generator=g))
     ref = O.attention_core(q, k, v, heads)
-    qd = q.reshape(-1, C).half().to(DEV)
-    kv = torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half().to(DEV)     # [K | V] rows, as the context GEMM writes
-    img = torch.empty(hip.xattn_image_bytes(batch, heads, d), dtype=torch.uint8, device=DEV)
-    out = torch.empty(batch * Lq, C, dtype=torch.float16, device=DEV)
-    out_f = torch.empty_like(out)
+    qd = gin(q.reshape(-1, C).half())
+    kv = gin(torch.cat([k.reshape(-1, C), v.reshape(-1, C)], dim=1).half())        # [K | V] rows, as the context GEMM writes
+    img = gout(1, hip.xattn_image_bytes(batch, heads, d), dtype=torch.uint8, guard_rows=1)
+    out = gout(batch * Lq, C)
+    out_f = gout(batch * Lq, C)
     desc = hip.AttnDesc(batch, heads, Lq, Lk, d, C, 2 * C, 2 * C, C, d ** -0.5)
     hip.xattn_pack_kv(kv.data_ptr(), kv.data_ptr() + 2 * C, batch, Lk, heads, d, 2 * C, 2 * C, img.data_ptr())
     hip.xattn(desc, qd.data_ptr(), img.data_ptr(), out.data_ptr())
@@ -787,6 +836,7 @@ def test_xattn_short_keys(hiplib, batch, heads, Lq, Lk, d):
     torch.cuda.synchronize()
     close(out.reshape(batch, Lq, C), ref)
     assert (out.float() - out_f.float()).abs().max().item() <= 2e-3 * ref.abs().max().item() + 1e-3
+    check_all(out, out_f, img, qd, kv)
 
 
 def test_xattn_rejects_long_keys(hiplib):
@@ -820,14 +870,15 @@ def test_flash_attn_masked(hiplib, batch, heads, L, d, causal, pad):
     else:
         add = add.expand(batch, L, L)
     ref = O.attention_core(q, k, v, heads, mask=add)
-    qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
+    qd, kd, vd = (gin(t.reshape(-1, C).half()) for t in (q, k, v))
     vm = valid.to(DEV)
-    out = torch.empty(batch * L, C, dtype=torch.float16, device=DEV)
+    out = gout(batch * L, C)
     desc = hip.AttnDesc(batch, heads, L, L, d, C, C, C, C, d ** -0.5)
     hip.flash_attn_masked(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), vm.data_ptr() if pad else 0, causal,
                           out.data_ptr())
     torch.cuda.synchronize()
     close(out.reshape(batch, L, C), ref)
+    check_all(out, qd, kd, vd)
 
 
 def test_gemm_gelu(hiplib):
@@ -839,13 +890,14 @@ def test_gemm_gelu(hiplib):
         W = h16(torch.randn(N, K, generator=g) * K ** -0.5)
         bias = torch.randn(N, generator=g)
         ref = F.gelu(F.linear(A, W, bias))
-        Ad, Wd, bd = A.half().to(DEV), W.half().to(DEV), bias.to(DEV)
-        out = torch.empty(M, N, dtype=torch.float16, device=DEV)
+        Ad, Wd, bd = gin(A.half()), gw(W), gvec(bias)
+        out = gout(M, N)
         dsc = hip.GemmDesc(M, N, K, K, N, 0, hip.EPI_BIAS | hip.EPI_GELU, 1, 0, 1.0, split)
         w = ws(hip.gemm_workspace_bytes(dsc))
         hip.gemm(dsc, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), w.data_ptr(), w.numel())
         torch.cuda.synchronize()
         close(out, ref)
+        check_all(out, Ad, Wd, bd)
 
 
 def test_flash_attn_forced_rescale(hiplib):
@@ -859,12 +911,13 @@ def test_flash_attn_forced_rescale(hiplib):
     v = h16(torch.randn(1, L, C, generator=g))
     k[0, 200, :d] = h16(q[0, 17, :d] * 4.0)      # spike in the 4th key tile for query 17 / head 0
     ref = O.attention_core(q, k, v, heads)
-    qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
-    out = torch.empty(L, C, dtype=torch.float16, device=DEV)
+    qd, kd, vd = (gin(t.reshape(-1, C).half()) for t in (q, k, v))
+    out = gout(L, C)
     desc = hip.AttnDesc(1, heads, L, L, d, C, C, C, C, d ** -0.5)
     hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
     torch.cuda.synchronize()
     close(out.reshape(1, L, C), ref)
+    check_all(out, qd, kd, vd)
 
 
 @pytest.mark.parametrize("L,boost", [(1024, (1.3, 1.8, 2.5, 4.0)), (4096, (1.5, 3.0)), (512, ())])
@@ -885,16 +938,17 @@ def test_flash_attn_deferred_max_long_keys(hiplib, L, boost):
         for qi in (5 + 64 * i, 40 + 64 * i):
             k[0, key + (qi & 7), :d] = h16(q[0, qi, :d] * f)
     ref = O.attention_core(q, k, v, heads)
-    qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
+    qd, kd, vd = (gin(t.reshape(-1, C).half()) for t in (q, k, v))
     desc = hip.AttnDesc(1, heads, L, L, d, C, C, C, C, d ** -0.5)
     outs = []
     for _ in range(2):
-        out = torch.empty(L, C, dtype=torch.float16, device=DEV)
+        out = gout(L, C)
         hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
         torch.cuda.synchronize()
         outs.append(out)
     close(outs[0].reshape(1, L, C), ref)
     assert torch.equal(outs[0], outs[1])
+    check_all(*outs, qd, kd, vd)
 
 
 @pytest.mark.parametrize("gain", [6.0, 30.0])
@@ -912,11 +966,12 @@ def test_flash_attn_msub_large_logits(hiplib, gain):
     k = h16(torch.randn(1, L, C, generator=g) * gain ** 0.5)
     v = h16(torch.randn(1, L, C, generator=g))
     ref = O.attention_core(q, k, v, heads)
-    qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
-    out = torch.empty(L, C, dtype=torch.float16, device=DEV)
+    qd, kd, vd = (gin(t.reshape(-1, C).half()) for t in (q, k, v))
+    out = gout(L, C)
     desc = hip.AttnDesc(1, heads, L, L, d, C, C, C, C, d ** -0.5)
     hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
     torch.cuda.synchronize()
+    check_all(out, qd, kd, vd)
     got = out.float().cpu().reshape(1, L, C)
     assert torch.isfinite(got).all()
     err = (got - ref).abs().max().item()
@@ -940,10 +995,10 @@ def test_flash_attn_wide_range_flag(hiplib):
     k = h16(torch.randn(1, L, C, generator=g) * gain ** 0.5)
     v = h16(torch.randn(1, L, C, generator=g))
     ref = O.attention_core(q, k, v, heads)
-    qd, kd, vd = (t.reshape(-1, C).half().to(DEV) for t in (q, k, v))
+    qd, kd, vd = (gin(t.reshape(-1, C).half()) for t in (q, k, v))
     errs = []
     for flags in (0, hip.ATTN_WIDE_RANGE):
-        out = torch.full((L, C), float("nan"), dtype=torch.float16, device=DEV)
+        out = gout(L, C)
         desc = hip.AttnDesc(1, heads, L, L, d, C, C, C, C, d ** -0.5, flags)
         hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
         torch.cuda.synchronize()
@@ -952,6 +1007,7 @@ def test_flash_attn_wide_range_flag(hiplib):
         errs.append((got - ref).abs().max().item())
         if flags:
             close(got, ref, rel=2e-3, abs_frac=4e-3)
+        check_all(out, qd, kd, vd)
     print(f"|scaled score| ~1300: max abs err {errs[0]:.3e} (matrix-pipe softmax argument) vs {errs[1]:.3e} (RCDM_ATTN_WIDE_RANGE)")
     assert errs[1] < errs[0]
 
@@ -969,12 +1025,13 @@ def test_temporal_attn(hiplib, b, frames, pixels, heads, d):
 
     o = O.attention_core(regroup(q), regroup(k), regroup(v), heads)
     ref = o.reshape(b, pixels, frames, C).permute(0, 2, 1, 3).reshape(b * frames * pixels, C)
-    out = torch.empty(b * frames * pixels, C, dtype=torch.float16, device=DEV)
+    out = gout(b * frames * pixels, C)
     desc = hip.TemporalAttnDesc(b, frames, pixels, heads, d, 3 * C, C, d ** -0.5)
-    qkv_d = qkv.half().to(DEV)
+    qkv_d = gin(qkv.half())
     hip.temporal_attn(desc, qkv_d.data_ptr(), out.data_ptr())
     torch.cuda.synchronize()
     close(out, ref)
+    check_all(out, qkv_d)
 
 
 def test_timestep_embed_and_small_linear(hiplib):
@@ -982,25 +1039,26 @@ def test_timestep_embed_and_small_linear(hiplib):
     g = torch.Generator().manual_seed(2)
     t = torch.tensor([981.0, 981.0, 1.0])
     ref = O.timestep_embedding(t, 320)
-    out = torch.empty(3, 320, device=DEV)
-    t_d = t.to(DEV)
+    out = gout(3, 320, dtype=torch.float32)
+    t_d = gvec(t)
     hip.timestep_embed(t_d.data_ptr(), 3, 320, out.data_ptr())
     torch.cuda.synchronize()
     assert (out.cpu() - ref).abs().max() < 2e-4
     W1 = h16(torch.randn(1280, 320, generator=g) * 0.05)
     b1 = torch.randn(1280, generator=g)
     ref2 = F.silu(F.linear(ref, W1, b1))
-    o2 = torch.empty(3, 1280, device=DEV)
-    W1d, b1d = W1.half().to(DEV), b1.to(DEV)
+    o2 = gout(3, 1280, dtype=torch.float32)
+    W1d, b1d = gw(W1), gvec(b1)
     hip.small_linear(out.data_ptr(), 3, 320, W1d.data_ptr(), b1d.data_ptr(), 1280, 0, 1, o2.data_ptr())
     W2 = h16(torch.randn(200, 1280, generator=g) * 0.03)
     ref3 = F.linear(F.silu(ref2), W2)
-    o3 = torch.empty(3, 200, device=DEV)
-    W2d = W2.half().to(DEV)
+    o3 = gout(3, 200, dtype=torch.float32)
+    W2d = gw(W2)
     hip.small_linear(o2.data_ptr(), 3, 1280, W2d.data_ptr(), 0, 200, 1, 0, o3.data_ptr())
     torch.cuda.synchronize()
     close(o2, ref2, rel=1e-3, abs_frac=1e-3)
     close(o3, ref3, rel=1e-3, abs_frac=1e-3)
+    check_all(out, o2, o3, t_d, W1d, b1d, W2d)
 
 
 def test_layout_and_ddim(hiplib):
@@ -1011,21 +1069,24 @@ def test_layout_and_ddim(hiplib):
     mask = (torch.rand(2 * S, 1, f, H, W, generator=g) > 0.5).float()
     masked = torch.randn(2 * S, 4, f, H, W, generator=g)
     ref_in = torch.cat([torch.cat([lat] * 2), mask, masked], dim=1)       # RCDMs_pipeline.py:482-486
-    rows = torch.full((2 * S * f * H * W, 64), float("nan"), dtype=torch.float16, device=DEV)
-    lat0, mask_d, masked_d = lat.to(DEV), mask.to(DEV), masked.to(DEV)
+    rows = gout(2 * S * f * H * W, 64)
+    lat0, mask_d, masked_d = gvec(lat), gvec(mask), gvec(masked)
     hip.assemble_input(lat0.data_ptr(), mask_d.data_ptr(), masked_d.data_ptr(), S, 2, f, H, W, rows.data_ptr(), 64, 64)
     torch.cuda.synchronize()
     close(rows_to_5d(rows, 2 * S, 9, f, H, W), ref_in, rel=1e-3, abs_frac=1e-3)
     assert (rows[:, 9:] == 0).all()
+    check_all(rows, lat0, mask_d, masked_d)
     # generic converters round-trip
     x = torch.randn(3, 9, f, H, W, generator=g)
-    r2 = torch.empty(3 * f * H * W, 16, dtype=torch.float16, device=DEV)
-    x_d = x.to(DEV)
+    r2 = gout(3 * f * H * W, 16)
+    x_d = gvec(x)
     hip.ncfhw_to_rows(x_d.data_ptr(), 3, 9, f, H, W, r2.data_ptr(), 16, 16)
-    back = torch.empty(3, 9, f, H, W, device=DEV)
+    back_h = gout(1, 3 * 9 * f * H * W, dtype=torch.float32, guard_rows=1)
+    back = back_h.view(3, 9, f, H, W)
     hip.rows_to_ncfhw(r2.data_ptr(), 16, 3, 9, f, H, W, back.data_ptr())
     torch.cuda.synchronize()
     assert torch.equal(back.cpu(), x.half().float())
+    check_all(r2, back_h, x_d)
     # CFG + DDIM step against the oracle scheduler
     sched = O.DDIMOracle(); sched.set_timesteps(20)
     eps = h16(torch.randn(2 * S, 4, f, H, W, generator=g))
@@ -1036,9 +1097,11 @@ def test_layout_and_ddim(hiplib):
         pt = int(t) - 1000 // 20
         a_t = sched.alphas_cumprod[int(t)]; a_p = sched.alphas_cumprod[pt] if pt >= 0 else torch.tensor(1.0)
         coef.append([a_t.sqrt(), (1 - a_t).sqrt(), a_p.sqrt(), (1 - a_p).sqrt()])
-    coef = torch.tensor(coef, dtype=torch.float32).to(DEV)
+    coef = gvec(torch.tensor(coef, dtype=torch.float32))
     step = torch.tensor([3], dtype=torch.int32, device=DEV)
-    lat_d = lat.clone().to(DEV)
+    lat_h = gout(1, lat.numel(), dtype=torch.float32, guard_rows=1)     # in place: the state sits between NaN guard bands
+    lat_h[0].copy_(lat.reshape(-1))
+    lat_d = lat_h.view(lat.shape)
     hip.cfg_ddim_step(eps_rows.data_ptr(), 32, lat_d.data_ptr(), S, 2, f, H, W, gs, coef.data_ptr(), step.data_ptr())
     hip.advance_step(step.data_ptr())
     torch.cuda.synchronize()
@@ -1046,6 +1109,7 @@ def test_layout_and_ddim(hiplib):
     ref = sched.step(e_u + gs * (e_c - e_u), sched.timesteps[3], lat)
     assert (lat_d.cpu() - ref).abs().max() < 1e-5
     assert int(step.item()) == 4
+    check_all(lat_h, eps_rows, coef)
 
 
 def test_cfg_pndm_step_vs_scheduler(hiplib):
@@ -1060,10 +1124,12 @@ def test_cfg_pndm_step_vs_scheduler(hiplib):
     sched.set_timesteps(n)
     orc = O.PNDMOracle(beta_schedule="scaled_linear"); orc.set_timesteps(n)
     assert torch.equal(sched.timesteps, orc.timesteps)
-    tab = sched.plms_table().to(DEV)
+    tab = gvec(sched.plms_table())
     lat = torch.randn(S, 4, f, H, W, generator=g)
-    lat_d = lat.clone().to(DEV)
-    hist = torch.full((5, S * 4 * f * H * W), float("nan"), device=DEV)   # (no initialisation needed: NaN-filled)
+    lat_h = gout(1, lat.numel(), dtype=torch.float32, guard_rows=1)     # in place: the state sits between NaN guard bands
+    lat_h[0].copy_(lat.reshape(-1))
+    lat_d = lat_h.view(lat.shape)
+    hist = gout(5, S * 4 * f * H * W, dtype=torch.float32, guard_rows=1)  # (no initialisation needed: NaN-filled)
     step = torch.zeros(1, dtype=torch.int32, device=DEV)
     x, xo = lat.clone(), lat.clone()
     for i, t in enumerate(sched.timesteps.tolist()):
@@ -1078,6 +1144,7 @@ def test_cfg_pndm_step_vs_scheduler(hiplib):
         xo = orc.step(e, t, xo)
         assert (lat_d.cpu() - x).abs().max() < 2e-5 * max(1.0, x.abs().max().item()), i
         assert (x - xo).abs().max() < 2e-5 * max(1.0, x.abs().max().item()), i
+        check_all(lat_h, hist, rows, tab)
     assert int(step.item()) == n + 1
 
 
@@ -1099,3 +1166,599 @@ def test_graph_capture_replay(hiplib):
         gr.launch()
         s.synchronize()
     close(out, A.float().cpu() @ W.float().cpu().t())
+
+
+# ------------------------------------------------------------------------------------------------
+# Layouts the engine uses and no test above runs: every row stride wider than its operand, all of them at once, the pad
+# columns poisoned (inputs) or NaN (outputs).  lda = c_in + 8, lda2 = c_in2 + 16, ldc = c_out + 24, ldr = c_out + 16,
+# ldt = c_out + 8: all different, so a stride taken from the wrong field shows too.
+def _gn_rows(x2d, samples, rps, C, groups, eps, dtype=torch.float64):
+    """(mean, rstd) [samples][groups] of rows [samples * rps][C] in `dtype` (biased variance, torch.nn.GroupNorm)."""
+    v = x2d.to(dtype).reshape(samples, rps, groups, C // groups)
+    mean = v.mean(dim=(1, 3))
+    var = v.var(dim=(1, 3), unbiased=False)
+    return mean, (var + eps).rsqrt()
+
+
+PADDED_CONVS = [
+    # form, b, f, H, W, cin, cin2, cout, split, variant   (per form: a ragged case, then a production-shaped one)
+    ("plain", 2, 3, 10, 6, 72, 0, 72, 1, 1),
+    ("plain", 2, 5, 16, 16, 320, 0, 320, 0, -1),
+    ("stride2", 1, 3, 9, 7, 72, 0, 40, 1, 2),           # odd sides: h_out = 5, w_out = 4
+    ("stride2", 2, 5, 16, 16, 320, 0, 320, 0, -1),      # Downsample3D
+    ("up1", 1, 3, 5, 3, 72, 0, 72, 1, 1),
+    ("up1", 2, 5, 8, 8, 640, 0, 640, 0, -1),            # Upsample3D folded into the conv
+    ("up2", 1, 5, 16, 16, 64, 0, 96, 0, 6),             # phase form: N tail of a 320-wide tile
+    ("up2", 1, 10, 8, 8, 640, 0, 640, 0, 6),
+    ("add1x1", 2, 3, 10, 6, 128, 64, 72, 1, 1),
+    ("add1x1", 2, 5, 8, 8, 640, 1280, 640, 0, -1),      # conv2 + conv_shortcut of an up-block ResNet
+    ("gnstat", 1, 5, 12, 10, 64, 0, 192, 2, 1),         # 600 rows: M tail on every tile height
+    ("gnstat", 2, 5, 16, 16, 128, 0, 320, 4, 9),
+    ("add1x1_gnstat", 1, 5, 12, 10, 64, 64, 192, 2, 1),
+    ("add1x1_gnstat", 2, 5, 16, 16, 128, 192, 320, 4, 9),
+    ("wino", 3, 2, 6, 10, 64, 128, 72, 3, -1),          # N tail, second input, forced split-K
+    ("wino", 2, 5, 16, 16, 320, 0, 320, 0, -1),
+    ("wino_gn", 1, 5, 12, 10, 64, 0, 192, 0, -1),       # the norm in the input transform + the next norm's partials
+    ("wino_gn", 2, 5, 16, 16, 640, 0, 640, 0, -1),
+]
+
+
+@pytest.mark.parametrize("form,b,f,H,W,cin,cin2,cout,split,variant", PADDED_CONVS)
+def test_conv_padded_strides(hiplib, form, b, f, H, W, cin, cin2, cout, split, variant):
+    """Every convolution form with lda > c_in, lda2 > c_in2, ldc > c_out, ldr > c_out and ldt > c_out together (an up-block
+    reads a concat buffer and writes into one): against the fp32 convolution of the f16-rounded operands."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(4000 + cin + cin2 + cout + H)
+    up2, wino = form == "up2", form.startswith("wino")
+    stride = 2 if form == "stride2" else 1
+    up = 1 if form == "up1" else 2 if up2 else 0
+    gn_in = form == "wino_gn"
+    x = h16(torch.randn(b, cin, f, H, W, generator=g) * 1.5 + 0.3)
+    w = h16(torch.randn(cout, cin, 3, 3, generator=g) * (9 * cin) ** -0.5)
+    bias, temb = torch.randn(cout, generator=g), torch.randn(b, cout, generator=g)
+    gamma, beta = torch.rand(cin, generator=g) + 0.5, torch.randn(cin, generator=g) * 0.3
+    xin = F.silu(O.group_norm_cross_frame(x, gamma, beta, 32, 1e-5)) if gn_in else x
+    xin = F.interpolate(xin, scale_factor=[1.0, 2.0, 2.0], mode="nearest") if up else xin
+    ref = O.conv_frames(xin, w, bias, stride=stride, padding=1)
+    Ho, Wo = ref.shape[-2:]
+    M = b * f * Ho * Wo
+    epi = hip.EPI_BIAS if up2 else hip.EPI_BIAS | hip.EPI_ROWVEC | hip.EPI_RESIDUAL     # the phase form takes a bias only
+    lda, lda2, ldc, ldr, ldt = cin + 8, cin2 + 16, cout + 24, cout + 16, cout + 8
+    x2d = w2 = None
+    if cin2:
+        x2 = h16(torch.randn(b, cin2, f, H, W, generator=g))
+        w2 = h16(torch.randn(cout, cin2, generator=g) * cin2 ** -0.5)
+        ref = ref + torch.einsum("oc,bcfhw->bofhw", w2, x2)
+        x2d = rows_from_5d(x2, lda2)
+    res = h16(torch.randn(ref.shape, generator=g))
+    if not up2:
+        ref = ref + temb[:, :, None, None, None] + res
+    xd, rd = rows_from_5d(x, lda), rows_from_5d(res, ldr)
+    w32, bd, td = gvec(w), gvec(bias), gin(temb, ldt, guard_rows=8)
+    out = gout(M, cout, ldc)
+    d = hip.ConvDesc(b * f, H, W, cin, cout, stride, up, lda, ldc, 0 if up2 else ldr, epi, 1 if up2 else f * Ho * Wo,
+                     0 if up2 else ldt, 1.0, split, 0, 0, cin2, lda2 if cin2 else 0)
+    ptrs = (0, 0) if up2 else (td.data_ptr(), rd.data_ptr())
+    ins = [xd, w32, bd] + ([] if up2 else [td, rd]) + ([x2d] if cin2 else [])
+    outs = [out]
+    if wino:
+        U = gout(16 * cout, cin)
+        hip.pack_conv3x3_wino(w32.data_ptr(), cout, cin, U.data_ptr())
+        w2d = gw(w2) if cin2 else None
+        gd, bed = gvec(gamma), gvec(beta)
+        assert hip.conv3x3_wino_supported(d)
+        gnd = god = stat = part = None
+        if gn_in:
+            gnd = hip.GroupNormDesc(b, f * H * W, cin, 32, lda, lda, 1e-5, 1)
+            stat = gout(1, b * 32 * 2, dtype=torch.float32, guard_rows=1)
+            gws = ws(hip.groupnorm_workspace_bytes(gnd))
+            hip.groupnorm_stats(gnd, xd.data_ptr(), stat.data_ptr(), gws.data_ptr(), gws.numel())
+            god = hip.GroupNormDesc(b, f * H * W, cout, 32, ldc, ldc, 1e-5, 0)
+            part = ws(b * 32 * (f * H * W // 4) * 3 * 4)
+            outs.append(stat)
+        wsb = ws(hip.conv3x3_wino_workspace_bytes(d))
+        hip.conv3x3_wino(d, xd.data_ptr(), U.data_ptr(), bd.data_ptr(), td.data_ptr(), rd.data_ptr(), out.data_ptr(),
+                         wsb.data_ptr(), wsb.numel(), x2=x2d.data_ptr() if cin2 else 0, W2=w2d.data_ptr() if cin2 else 0,
+                         gn=gnd, gn_stat=stat.data_ptr() if gn_in else 0, gn_gamma=gd.data_ptr() if gn_in else 0,
+                         gn_beta=bed.data_ptr() if gn_in else 0, gn_out=god, gn_out_partial=part.data_ptr() if gn_in else 0)
+        torch.cuda.synchronize()
+        outs.append(U)
+        ins += [gd, bed] + ([w2d] if cin2 else [])
+        if gn_in:   # the partial statistics the output transform left: finalized, they are the statistics of the stored rows
+            st = gout(1, b * 32 * 2, dtype=torch.float32, guard_rows=1)
+            hip.groupnorm_finalize(b, 32, f * H * W // 4, 1e-5, part.data_ptr(), st.data_ptr())
+            torch.cuda.synchronize()
+            mean, rstd = _gn_rows(out[:, :cout].cpu(), b, f * H * W, cout, 32, 1e-5)
+            got = st.cpu().double().reshape(b, 32, 2)
+            assert torch.allclose(got[..., 0], mean, rtol=2e-5, atol=1e-6) and torch.allclose(got[..., 1], rstd, rtol=2e-5, atol=1e-6)
+            outs.append(st)
+    else:
+        if up2:
+            wp = gout(4 * cout, 4 * cin)
+            hip.pack_conv3x3_up2(w32.data_ptr(), cout, cin, wp.data_ptr())
+        else:
+            wp = gout(cout, 9 * cin)
+            hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
+        outs.append(wp)
+        wk = gw(torch.cat([wp, w2.half().to(DEV)], dim=1)) if cin2 else wp
+        gnstat = form.endswith("gnstat")
+        hip.set_igemm_variant(variant)
+        try:
+            if up2:
+                assert hip.conv3x3_up2_supported(d)
+            wsb = ws(hip.conv3x3_workspace_bytes(d))
+            tail = (bd.data_ptr(), *ptrs, out.data_ptr(), wsb.data_ptr(), wsb.numel())
+            if gnstat:   # the split-K reduce pass also leaves the statistics of the norm that reads `out` (row stride ldc) next
+                gnd = hip.GroupNormDesc(b, f * H * W, cout, 32, ldc, cout + 8, 1e-5, 1)
+                assert hip.conv3x3_gnstat_ok(d, gnd) and hip.groupnorm_prestat_ok(gnd)
+                gk = ws(hip.groupnorm_workspace_bytes(gnd))
+                if cin2:
+                    hip.conv3x3_add1x1_gnstat(d, gnd, xd.data_ptr(), x2d.data_ptr(), wk.data_ptr(), *tail, gk.data_ptr(), gk.numel())
+                else:
+                    hip.conv3x3_gnstat(d, gnd, xd.data_ptr(), wk.data_ptr(), *tail, gk.data_ptr(), gk.numel())
+                g2, b2 = torch.randn(cout, generator=g), torch.randn(cout, generator=g)
+                g2d, b2d = gvec(g2), gvec(b2)
+                y = gout(M, cout, cout + 8)
+                hip.groupnorm_silu_prestat(gnd, out.data_ptr(), g2d.data_ptr(), b2d.data_ptr(), y.data_ptr(), gk.data_ptr(), gk.numel())
+                torch.cuda.synchronize()
+                yref = F.silu(O.group_norm_cross_frame(rows_to_5d(out, b, cout, f, H, W), g2, b2, 32, 1e-5))
+                close(rows_to_5d(y, b, cout, f, H, W), yref)
+                outs.append(y)
+                ins += [g2d, b2d]
+            elif cin2:
+                hip.conv3x3_add1x1(d, xd.data_ptr(), x2d.data_ptr(), wk.data_ptr(), *tail)
+            else:
+                hip.conv3x3(d, xd.data_ptr(), wk.data_ptr(), *tail)
+            torch.cuda.synchronize()
+        finally:
+            hip.set_igemm_variant(-1)
+        if cin2:
+            ins.append(wk)
+    close(rows_to_5d(out, b, cout, f, Ho, Wo), ref)
+    check_all(*outs, *ins)
+
+
+@pytest.mark.parametrize("variant", [1, 2, 5, 6, 8, 9])
+@pytest.mark.parametrize("split", [1, 2])
+def test_conv3x3_dup_rows(hiplib, variant, split):
+    """rcdm_conv3x3_desc.dup_rows (the shared CFG prefix): the copy dup_rows = M + 3 further down is bit-identical and the
+    three rows between the two images of the output stay untouched."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(6)
+    n_img, H, W, cin, cout = 3, 10, 10, 64, 320
+    M = n_img * H * W
+    x = h16(torch.randn(1, cin, n_img, H, W, generator=g))
+    w = h16(torch.randn(cout, cin, 3, 3, generator=g) * (9 * cin) ** -0.5)
+    bias = torch.randn(cout, generator=g)
+    ref = O.conv_frames(x, w, bias, stride=1, padding=1)
+    lda, ldc = cin + 8, cout + 8
+    xd, w32, bd = rows_from_5d(x, lda), gvec(w), gvec(bias)
+    wp = gout(cout, 9 * cin)
+    hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
+    out = gout(2 * M + 3, cout, ldc)
+    d = hip.ConvDesc(n_img, H, W, cin, cout, 1, 0, lda, ldc, 0, hip.EPI_BIAS, 1, 0, 1.0, split, 0, M + 3)
+    hip.set_igemm_variant(variant)
+    try:
+        wsb = ws(hip.conv3x3_workspace_bytes(d))
+        hip.conv3x3(d, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), wsb.data_ptr(), wsb.numel())
+        torch.cuda.synchronize()
+    finally:
+        hip.set_igemm_variant(-1)
+    close(rows_to_5d(out[:M], 1, cout, n_img, H, W), ref)
+    assert torch.equal(out[:M, :cout], out[M + 3:, :cout]), "the duplicate rows differ"
+    assert torch.isnan(out[M:M + 3].float()).all(), "the rows between the two copies were written"
+    check_all(out, wp, xd, w32, bd)
+
+
+@pytest.mark.parametrize("n_img,H,W,cin,cout", [(3, 6, 10, 72, 40), (2, 16, 16, 128, 128)])
+def test_conv3x3_pad_after_only(hiplib, n_img, H, W, cin, cout):
+    """pad_after_only = 1 (F.pad(x, (0, 1, 0, 1)) + a stride-2 conv without padding, the VAE encoder's downsampler) with padded
+    row strides; an odd side is refused (rcdm.h: even h_in and w_in)."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(60 + cin)
+    x = h16(torch.randn(1, cin, n_img, H, W, generator=g))
+    w = h16(torch.randn(cout, cin, 3, 3, generator=g) * (9 * cin) ** -0.5)
+    bias = torch.randn(cout, generator=g)
+    ref = O.conv_frames(F.pad(x, (0, 1, 0, 1)), w, bias, stride=2, padding=0)
+    Ho, Wo = ref.shape[-2:]
+    assert (Ho, Wo) == (H // 2, W // 2)
+    lda, ldc = cin + 8, cout + 24
+    xd, w32, bd = rows_from_5d(x, lda), gvec(w), gvec(bias)
+    wp = gout(cout, 9 * cin)
+    hip.pack_conv3x3(w32.data_ptr(), cout, cin, cin, wp.data_ptr())
+    out = gout(n_img * Ho * Wo, cout, ldc)
+    d = hip.ConvDesc(n_img, H, W, cin, cout, 2, 0, lda, ldc, 0, hip.EPI_BIAS, 1, 0, 1.0, 1, 1)
+    wsb = ws(hip.conv3x3_workspace_bytes(d))
+    hip.conv3x3(d, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), wsb.data_ptr(), wsb.numel())
+    torch.cuda.synchronize()
+    close(rows_to_5d(out, 1, cout, n_img, Ho, Wo), ref)
+    check_all(out, wp, xd, w32, bd)
+    for h_odd, w_odd in ((H + 1, W), (H, W + 1)):
+        bad = hip.ConvDesc(n_img, h_odd, w_odd, cin, cout, 2, 0, lda, ldc, 0, hip.EPI_BIAS, 1, 0, 1.0, 1, 1)
+        with pytest.raises(hip.RcdmError, match="RCDM_ESHAPE"):
+            hip.conv3x3(bad, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), wsb.data_ptr(), wsb.numel())
+    check_all(out, xd)
+
+
+@pytest.mark.parametrize("n_img,H,W,cin,cout,up,with_bias", [
+    (10, 64, 64, 320, 4, 0, True),      # conv_out: 320 -> 4 channels padded to 8, ten 64x64 latent images
+    (3, 5, 7, 320, 4, 0, True),         # a small ragged image
+    (3, 5, 7, 72, 4, 0, False),
+    (3, 4, 6, 64, 64, 1, True),         # the upsampling gather into a wider buffer
+])
+def test_conv_taps_gather(hiplib, n_img, H, W, cin, cout, up, with_bias):
+    """rcdm_gemm over nine stacked tap planes + rcdm_conv_taps_gather against the fp32 conv3x3: upsample = 0 at conv_out's
+    geometry (the output channels zero-padded to 8 as the UNet program does) and upsample = 1, both with ldc > c_out."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(80 + cin + H + up)
+    cp = (cout + 7) // 8 * 8
+    x = h16(torch.randn(1, cin, n_img, H, W, generator=g))
+    w = h16(torch.randn(cout, cin, 3, 3, generator=g) * (9 * cin) ** -0.5)
+    bias = torch.randn(cout, generator=g)
+    xin = F.interpolate(x, scale_factor=[1.0, 2.0, 2.0], mode="nearest") if up else x
+    ref = O.conv_frames(xin, w, bias if with_bias else None, stride=1, padding=1)
+    wpad = torch.cat([w, torch.zeros(cp - cout, cin, 3, 3)])
+    bpad = torch.cat([bias, torch.zeros(cp - cout)])
+    M, lda, ldp, ldc = n_img * H * W, cin + 8, 9 * cp + 8, cp + 8
+    xd, W9, bd = rows_from_5d(x, lda), gw(wpad.permute(2, 3, 0, 1).reshape(9 * cp, cin)), gvec(bpad)
+    P = gout(M, 9 * cp, ldp)
+    d = hip.GemmDesc(M, 9 * cp, cin, lda, ldp, 0, 0, 1, 0, 1.0, 0, 0)
+    wsb = ws(hip.gemm_workspace_bytes(d))
+    hip.gemm(d, xd.data_ptr(), W9.data_ptr(), 0, 0, 0, P.data_ptr(), wsb.data_ptr(), wsb.numel())
+    out = gout(M << (2 * up), cp, ldc)
+    hip.conv_taps_gather(P.data_ptr(), ldp, n_img, H, W, cp, up, bd.data_ptr() if with_bias else 0, out.data_ptr(), ldc)
+    torch.cuda.synchronize()
+    got = rows_to_5d(out, 1, cp, n_img, H << up, W << up)
+    close(got[:, :cout], ref)
+    if cp > cout:
+        assert (got[:, cout:] == 0).all(), "the zero-padded output channels are not zero"
+    check_all(out, P, xd, W9, bd)
+
+
+@pytest.mark.parametrize("b,f,H,W,C,cross,silu", [
+    (2, 5, 8, 8, 320, True, True),       # 320 rows per sample: the single-launch form
+    (2, 3, 7, 9, 192, False, False),     # 63 rows per sample (ragged), per frame
+    (1, 5, 16, 16, 64, True, True),      # 1280 rows per sample: statistics / finalize / apply
+    (2, 5, 16, 16, 1920, True, True),    # cg = 60: the three-launch path at a production width
+])
+def test_groupnorm_padded_strides(hiplib, b, f, H, W, C, cross, silu):
+    """rcdm_groupnorm_silu with poisoned ldx > C and ldy > C on the single-launch and the three-launch form."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(50 + C)
+    x = h16(torch.randn(b, C, f, H, W, generator=g) * 2.0 + 0.7)
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    eps = 1e-5 if cross else 1e-6
+    if cross:
+        ref = O.group_norm_cross_frame(x, gamma, beta, 32, eps)
+    else:
+        x4 = x.permute(0, 2, 1, 3, 4).reshape(b * f, C, H, W)
+        ref = O.group_norm_per_frame(x4, gamma, beta, 32, eps).reshape(b, f, C, H, W).permute(0, 2, 1, 3, 4)
+    if silu:
+        ref = F.silu(ref)
+    ldx, ldy = C + 8, C + 24
+    xd = rows_from_5d(x, ldx)
+    y = gout(b * f * H * W, C, ldy)
+    samples, rps = (b, f * H * W) if cross else (b * f, H * W)
+    d = hip.GroupNormDesc(samples, rps, C, 32, ldx, ldy, eps, int(silu))
+    w = ws(hip.groupnorm_workspace_bytes(d))
+    gd, bd = gvec(gamma), gvec(beta)
+    hip.groupnorm_silu(d, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), y.data_ptr(), w.data_ptr(), w.numel())
+    torch.cuda.synchronize()
+    close(rows_to_5d(y, b, C, f, H, W), ref)
+    check_all(y, xd, gd, bd)
+
+
+GN_PARTS = [
+    # samples, rows per sample, C, groups
+    (3, 315, 72, 4),        # ragged rows, cg = 18
+    (2, 640, 320, 32),      # cross-frame norm of an 8x8-level ResNet block (5 frames x 128 ... rows), cg = 10
+    (10, 256, 1280, 32),    # per-frame norm at the 16x16 level, cg = 40
+    (1, 4100, 64, 32),      # one long sample, cg = 2
+]
+
+
+def _stat_bound(got, ref64, ref32, what, case):
+    """|kernel - fp64| against eight times the error of the plain torch fp32 evaluation of the same statistic (the factor: the
+    kernel's different but fixed order of additions)."""
+    err = (got.double() - ref64).abs().max().item()
+    yard = (ref32.double() - ref64).abs().max().item()
+    print(f"groupnorm {what} {case}: kernel max abs err {err:.3e}, torch fp32 yardstick {yard:.3e}, bound {8 * yard:.3e}")
+    assert err <= 8 * yard, f"{what}: {err:.3e} > 8 x {yard:.3e}"
+
+
+@pytest.mark.parametrize("samples,rps,C,groups", GN_PARTS)
+def test_groupnorm_stats_alone(hiplib, samples, rps, C, groups):
+    """rcdm_groupnorm_stats on its own against fp64, rows at a poisoned ldx > C; (mean, rstd) within 8x the error of torch's
+    fp32 evaluation of the same statistics."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(70 + C + rps)
+    x = (torch.randn(samples * rps, C, generator=g) * 2.0 + 0.7).half()
+    eps, ldx = 1e-5, C + 8
+    xd = gin(x, ldx)
+    stat = gout(1, samples * groups * 2, dtype=torch.float32, guard_rows=1)
+    d = hip.GroupNormDesc(samples, rps, C, groups, ldx, C, eps, 0)
+    w = ws(hip.groupnorm_workspace_bytes(d))
+    hip.groupnorm_stats(d, xd.data_ptr(), stat.data_ptr(), w.data_ptr(), w.numel())
+    torch.cuda.synchronize()
+    got = stat.cpu().reshape(samples, groups, 2)
+    assert torch.isfinite(got).all()
+    m64, r64 = _gn_rows(x, samples, rps, C, groups, eps)
+    m32, r32 = _gn_rows(x, samples, rps, C, groups, eps, torch.float32)
+    check_all(stat, xd)
+    _stat_bound(got[..., 0], m64, m32, "stats mean", (samples, rps, C, groups))
+    _stat_bound(got[..., 1], r64, r32, "stats rstd", (samples, rps, C, groups))
+
+
+@pytest.mark.parametrize("samples,rps,C,groups", GN_PARTS)
+@pytest.mark.parametrize("splits", [3, 7])
+def test_groupnorm_finalize_alone(hiplib, samples, rps, C, groups, splits):
+    """rcdm_groupnorm_finalize on its own: (count, mean, M2) partials of uneven row slices, formed in fp64 and rounded to fp32,
+    against the fp64 combination of those fp32 values; the yardstick is the same combination evaluated by torch in fp32."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(71 + C + rps)
+    x = (torch.randn(samples, rps, groups, C // groups, generator=g) * 2.0 + 0.7).half().double()
+    eps = 1e-5
+    cuts = [0] + [min(rps, (i + 1) * (rps // splits) + (3 if i % 2 == 0 and splits > 1 else 0)) for i in range(splits - 1)] + [rps]
+    part = torch.empty(samples, groups, splits, 3, dtype=torch.float64)
+    for i in range(splits):
+        v = x[:, cuts[i]:cuts[i + 1]]
+        mu = v.mean(dim=(1, 3))
+        part[:, :, i, 0] = v.shape[1] * v.shape[3]
+        part[:, :, i, 1] = mu
+        part[:, :, i, 2] = (v - mu[:, None, :, None]).pow(2).sum(dim=(1, 3))
+    part = part.float()
+
+    def combine(p):
+        n, mu, m2 = p[..., 0], p[..., 1], p[..., 2]
+        tot = n.sum(-1)
+        mean = (n * mu).sum(-1) / tot
+        var = (m2 + n * (mu - mean[..., None]).pow(2)).sum(-1) / tot
+        return mean, (var + eps).rsqrt()
+
+    (m64, r64), (m32, r32) = combine(part.double()), combine(part)
+    pd = gvec(part)
+    stat = gout(1, samples * groups * 2, dtype=torch.float32, guard_rows=1)
+    hip.groupnorm_finalize(samples, groups, splits, eps, pd.data_ptr(), stat.data_ptr())
+    torch.cuda.synchronize()
+    got = stat.cpu().reshape(samples, groups, 2)
+    assert torch.isfinite(got).all()
+    check_all(stat, pd)
+    _stat_bound(got[..., 0], m64, m32, "finalize mean", (samples, rps, C, groups, splits))
+    _stat_bound(got[..., 1], r64, r32, "finalize rstd", (samples, rps, C, groups, splits))
+
+
+@pytest.mark.parametrize("samples,rps,C,groups", GN_PARTS)
+@pytest.mark.parametrize("silu", [0, 1])
+def test_groupnorm_apply_alone(hiplib, samples, rps, C, groups, silu):
+    """rcdm_groupnorm_apply on its own: final (mean, rstd) pairs handed in, rows at poisoned ldx > C, output at ldy > C, against
+    the fp64 normalisation with those pairs."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(72 + C + rps)
+    x = (torch.randn(samples * rps, C, generator=g) * 2.0 + 0.7).half()
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    eps, ldx, ldy = 1e-5, C + 8, C + 24
+    m64, r64 = _gn_rows(x, samples, rps, C, groups, eps)
+    st = torch.stack([m64, r64], dim=-1).float()
+    v = x.double().reshape(samples, rps, groups, C // groups)
+    ref = (v - st[..., 0].double()[:, None, :, None]) * st[..., 1].double()[:, None, :, None]
+    ref = ref.reshape(samples * rps, C) * gamma.double() + beta.double()
+    if silu:
+        ref = F.silu(ref)
+    xd, sd, gd, bd = gin(x, ldx), gvec(st), gvec(gamma), gvec(beta)
+    y = gout(samples * rps, C, ldy)
+    d = hip.GroupNormDesc(samples, rps, C, groups, ldx, ldy, eps, silu)
+    hip.groupnorm_apply(d, xd.data_ptr(), sd.data_ptr(), gd.data_ptr(), bd.data_ptr(), y.data_ptr())
+    torch.cuda.synchronize()
+    close(y[:, :C], ref)
+    check_all(y, xd, sd, gd, bd)
+
+
+@pytest.mark.parametrize("M,C,pe", [(33, 64, False), (97, 768, False), (10, 1280, True), (2051, 320, False), (1, 200, False),
+                                    (20, 1000, True), (970, 2048, False)])
+def test_layernorm_padded_strides(hiplib, M, C, pe):
+    """rcdm_layernorm with poisoned ldx > C and ldy > C: a row statistic that runs into the pad columns shows."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(12 + C)
+    frames, rpf = 5, 2
+    x = h16(torch.randn(M, C, generator=g) * 3 + 1)
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    ref = F.layer_norm(x, (C,), gamma, beta, 1e-5)
+    table = O.sinusoid_table(C, frames)
+    if pe:
+        ref = ref + table[(torch.arange(M) // rpf) % frames]
+    ldx, ldy = C + 8, C + 24
+    xd = gin(x.half(), ldx)
+    y = gout(M, C, ldy)
+    d = hip.LayerNormDesc(M, C, ldx, ldy, 1e-5, rpf, frames)
+    gd, bd, td = gvec(gamma), gvec(beta), gvec(table)
+    hip.layernorm(d, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), td.data_ptr() if pe else 0, y.data_ptr())
+    torch.cuda.synchronize()
+    close(y[:, :C], ref)
+    check_all(y, xd, gd, bd, td)
+
+
+@pytest.mark.parametrize("batch,heads,Lq,Lk,d", [
+    (2, 8, 200, 85, 40),     # ragged query and key tiles
+    (3, 8, 64, 91, 80),
+    (1, 8, 130, 130, 160),
+    (2, 4, 96, 85, 8),
+    (1, 2, 70, 77, 16),
+    (1, 2, 67, 70, 32),
+])
+def test_flash_attn_padded_strides(hiplib, batch, heads, Lq, Lk, d):
+    """rcdm_flash_attn with q, k, v and the output each in a buffer of its own wider than heads * d: beside the LAST head lies
+    poison (NaN in the output), not the next head."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(4 + Lq + Lk + d)
+    C = heads * d
+    q = h16(torch.randn(batch, Lq, C, generator=g))
+    k = h16(torch.randn(batch, Lk, C, generator=g))
+    v = h16(torch.randn(batch, Lk, C, generator=g))
+    ref = O.attention_core(q, k, v, heads)
+    ldq, ldk, ldv, ldo = C + 8, C + 16, C + 24, C + 32
+    qd, kd, vd = gin(q.reshape(-1, C).half(), ldq), gin(k.reshape(-1, C).half(), ldk), gin(v.reshape(-1, C).half(), ldv)
+    out = gout(batch * Lq, C, ldo)
+    desc = hip.AttnDesc(batch, heads, Lq, Lk, d, ldq, ldk, ldv, ldo, d ** -0.5)
+    hip.flash_attn(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr())
+    torch.cuda.synchronize()
+    close(out[:, :C].reshape(batch, Lq, C), ref)
+    check_all(out, qd, kd, vd)
+
+
+@pytest.mark.parametrize("batch,heads,L,d,causal,pad", [
+    (2, 4, 97, 64, True, True),
+    (3, 2, 150, 40, False, True),
+    (1, 2, 70, 160, True, False),
+])
+def test_flash_attn_masked_padded_strides(hiplib, batch, heads, L, d, causal, pad):
+    """rcdm_flash_attn_masked with every row stride wider than heads * d, the pad columns poisoned."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(6 + L + d)
+    C = heads * d
+    q, k, v = (h16(torch.randn(batch, L, C, generator=g)) for _ in range(3))
+    valid = torch.ones(batch, L, dtype=torch.uint8)
+    if pad:
+        for b in range(batch):
+            valid[b, 20 + 7 * b:L - 6] = 0
+    add = (1.0 - valid.float())[:, None, :] * -10000.0
+    add = add + torch.full((L, L), -10000.0).triu_(1)[None] if causal else add.expand(batch, L, L)
+    ref = O.attention_core(q, k, v, heads, mask=add)
+    ldq, ldk, ldv, ldo = C + 8, C + 16, C + 24, C + 32
+    qd, kd, vd = gin(q.reshape(-1, C).half(), ldq), gin(k.reshape(-1, C).half(), ldk), gin(v.reshape(-1, C).half(), ldv)
+    vm = valid.to(DEV)
+    out = gout(batch * L, C, ldo)
+    desc = hip.AttnDesc(batch, heads, L, L, d, ldq, ldk, ldv, ldo, d ** -0.5)
+    hip.flash_attn_masked(desc, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), vm.data_ptr() if pad else 0, causal, out.data_ptr())
+    torch.cuda.synchronize()
+    close(out[:, :C].reshape(batch, L, C), ref)
+    check_all(out, qd, kd, vd)
+
+
+@pytest.mark.parametrize("b,frames,pixels,heads,d", [(2, 5, 64, 8, 40), (1, 5, 16, 8, 160), (2, 5, 33, 8, 8), (1, 3, 20, 4, 16)])
+def test_temporal_attn_padded_strides(hiplib, b, frames, pixels, heads, d):
+    """rcdm_temporal_attn with ldqkv > 3 C and ldo > C: beside v's last head lies poison."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(18 + pixels + d)
+    C = heads * d
+    qkv = h16(torch.randn(b * frames * pixels, 3 * C, generator=g))
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+
+    def regroup(x):
+        return x.reshape(b, frames, pixels, C).permute(0, 2, 1, 3).reshape(b * pixels, frames, C)
+
+    o = O.attention_core(regroup(q), regroup(k), regroup(v), heads)
+    ref = o.reshape(b, pixels, frames, C).permute(0, 2, 1, 3).reshape(b * frames * pixels, C)
+    ldqkv, ldo = 3 * C + 8, C + 24
+    out = gout(b * frames * pixels, C, ldo)
+    desc = hip.TemporalAttnDesc(b, frames, pixels, heads, d, ldqkv, ldo, d ** -0.5)
+    qkv_d = gin(qkv.half(), ldqkv)
+    hip.temporal_attn(desc, qkv_d.data_ptr(), out.data_ptr())
+    torch.cuda.synchronize()
+    close(out[:, :C], ref)
+    check_all(out, qkv_d)
+
+
+@pytest.mark.parametrize("N", [8, 72, 1000, 4096])
+@pytest.mark.parametrize("M", [1, 130])
+@pytest.mark.parametrize("scale", [0.25, 1.0])
+def test_softmax_rows_padded(hiplib, M, N, scale):
+    """rcdm_softmax_rows against fp64 on the f16-rounded logits, ldx > N (poisoned) and ldy > N; row 0 has a single
+    dominant logit.  Tolerance of tests/test_vae.py test_softmax_rows."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(9 + M + N)
+    x = (torch.randn(M, N, generator=g) * 3).half()
+    x[0, N // 3] = 60.0
+    want = torch.softmax(x.double() * scale, dim=-1)
+    ldx, ldy = N + 8, N + 16
+    xd = gin(x, ldx)
+    y = gout(M, N, ldy)
+    hip.softmax_rows(M, N, ldx, ldy, scale, xd.data_ptr(), y.data_ptr())
+    torch.cuda.synchronize()
+    got = y[:, :N].float().cpu()
+    assert torch.isfinite(got).all(), "non-finite output"
+    assert torch.allclose(got.double(), want, rtol=2e-3, atol=1e-6), (got.double() - want).abs().max()
+    check_all(y, xd)
+
+
+@pytest.mark.parametrize("rows", [1, 8])
+def test_timestep_embed_and_small_linear_rows(hiplib, rows):
+    """rcdm_timestep_embed and rcdm_small_linear at 1 and 8 rows, guarded outputs (fp32 against fp64 of the f16 weights)."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(3 + rows)
+    t = torch.linspace(1.0, 981.0, rows)
+    ref = O.timestep_embedding(t, 320)
+    out = gout(rows, 320, dtype=torch.float32)
+    t_d = gvec(t)
+    hip.timestep_embed(t_d.data_ptr(), rows, 320, out.data_ptr())
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all() and (out.cpu() - ref).abs().max() < 2e-4
+    W1 = h16(torch.randn(200, 320, generator=g) * 0.05)
+    b1 = torch.randn(200, generator=g)
+    ref2 = F.silu(F.linear(F.silu(out.cpu().double()), W1.double(), b1.double()))
+    o2 = gout(rows, 200, dtype=torch.float32)
+    W1d, b1d = gw(W1), gvec(b1)
+    hip.small_linear(out.data_ptr(), rows, 320, W1d.data_ptr(), b1d.data_ptr(), 200, 1, 1, o2.data_ptr())
+    torch.cuda.synchronize()
+    close(o2, ref2, rel=1e-3, abs_frac=1e-3)
+    check_all(out, o2, t_d, W1d, b1d)
+
+
+def test_converters_into_wider_rows(hiplib):
+    """rcdm_assemble_input / rcdm_ncfhw_to_rows into rows with ld > c_pad: the columns C..c_pad are zero, the columns
+    c_pad..ld untouched; rcdm_rows_to_ncfhw reads such rows back."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(9)
+    S, f, H, W = 2, 3, 5, 7
+    lat = torch.randn(S, 4, f, H, W, generator=g)
+    mask = (torch.rand(2 * S, 1, f, H, W, generator=g) > 0.5).float()
+    masked = torch.randn(2 * S, 4, f, H, W, generator=g)
+    ref_in = torch.cat([torch.cat([lat] * 2), mask, masked], dim=1)
+    rows = gout(2 * S * f * H * W, 16, 40)
+    lat0, mask_d, masked_d = gvec(lat), gvec(mask), gvec(masked)
+    hip.assemble_input(lat0.data_ptr(), mask_d.data_ptr(), masked_d.data_ptr(), S, 2, f, H, W, rows.data_ptr(), 40, 16)
+    torch.cuda.synchronize()
+    close(rows_to_5d(rows, 2 * S, 9, f, H, W), ref_in, rel=1e-3, abs_frac=1e-3)
+    assert (rows[:, 9:16] == 0).all()
+    check_all(rows, lat0, mask_d, masked_d)
+    x = torch.randn(3, 9, f, H, W, generator=g)
+    r2 = gout(3 * f * H * W, 16, 32)
+    x_d = gvec(x)
+    hip.ncfhw_to_rows(x_d.data_ptr(), 3, 9, f, H, W, r2.data_ptr(), 32, 16)
+    torch.cuda.synchronize()
+    assert torch.equal(rows_to_5d(r2, 3, 9, f, H, W), x.half().float()) and (r2[:, 9:16] == 0).all()
+    check_all(r2, x_d)
+    src = rows_from_5d(x, 32)           # poison beyond the 9 channels
+    back_h = gout(1, x.numel(), dtype=torch.float32, guard_rows=1)
+    hip.rows_to_ncfhw(src.data_ptr(), 32, 3, 9, f, H, W, back_h.data_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(back_h.view(x.shape).cpu(), x.half().float())
+    check_all(back_h, src)
+
+
+@pytest.mark.parametrize("reps,with_noise,clip", [(2, True, 10.0), (1, False, 0.0)])
+def test_cfg_unclip_step_padded_rows(hiplib, reps, with_noise, clip):
+    """rcdm_cfg_unclip_step reading f16 prediction rows with ld > E, poison beyond the E used columns, against the formula
+    of rcdm.h in fp64; the state sits between guard bands."""
+    from rcdms_amd import hip
+    g = torch.Generator().manual_seed(14 + reps)
+    n, E, ld, gs, steps, st = 3, 72, 88, 4.0, 4, 2
+    pred = (torch.randn(reps * n, E, generator=g) * 6).half()
+    lat = torch.randn(n, E, generator=g)
+    coef = torch.rand(steps, 3, generator=g) + 0.1
+    noise = torch.randn(steps, n, E, generator=g)
+    p = pred.double()
+    x0 = p[:n] + gs * (p[n:] - p[:n]) if reps == 2 else p
+    if clip > 0:
+        x0 = x0.clamp(-clip, clip)
+    c = coef.double()[st]
+    ref = c[0] * x0 + c[1] * lat.double() + (c[2] * noise[st].double() if with_noise else 0.0)
+    pd, cd, nd = gin(pred, ld), gvec(coef), gvec(noise)
+    lat_h = gout(1, n * E, dtype=torch.float32, guard_rows=1)
+    lat_h[0].copy_(lat.reshape(-1))
+    step = torch.tensor([st], dtype=torch.int32, device=DEV)
+    hip.cfg_unclip_step(pd.data_ptr(), ld, lat_h.data_ptr(), n, reps, E, gs, clip, cd.data_ptr(), nd.data_ptr() if with_noise else 0,
+                        step.data_ptr())
+    torch.cuda.synchronize()
+    got = lat_h[0].cpu().double().reshape(n, E)
+    assert (got - ref).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
+    check_all(lat_h, pd, cd, nd)

@@ -8,7 +8,8 @@ rows whose mean is large against their spread (the cancellation case of E[x^2] -
 import pytest
 import torch
 
-from tests.test_hip_kernels import DEV, close, h16, ws
+from tests.guard import check_all
+from tests.test_hip_kernels import DEV, close, gin, gout, gvec, gw, h16, ws
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +26,15 @@ def _producer(hip, Ap, Wp, bp, res, M, C, Kp, variant, dup=0):
     d = hip.GemmDesc(M, C, Kp, Kp, C, C, 1 | 4, 1, 0, 1.0, 1, dup)
     parts = hip.gemm_stat_parts(d)
     assert parts > 0
-    x = torch.full((M + dup, C), float("nan"), dtype=torch.float16, device=DEV)
-    stat = torch.full(((M + dup) * parts * 2,), float("nan"), dtype=torch.float32, device=DEV)
+    x = gout(M + dup, C)
+    stat_h = gout(1, (M + dup) * parts * 2, dtype=torch.float32, guard_rows=1)
+    stat = stat_h[0]
     lx = hip.Lnx(stat.data_ptr(), parts, M + dup, 0, 0, 0, 0, 1e-5, 0)
-    Ad, Wd, bd, Rd = Ap.half().to(DEV), Wp.half().to(DEV), bp.to(DEV), res.half().to(DEV)
+    Ad, Wd, bd, Rd = gin(Ap.half()), gw(Wp), gvec(bp), gin(res.half())
     hip.gemm_lnx(d, lx, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), 0, Rd.data_ptr(), x.data_ptr(), 0, 0)
     torch.cuda.synchronize()
     hip.set_igemm_variant(-1)
+    check_all(x, stat_h, Ad, Wd, bd, Rd)
     return x, stat, parts
 
 
@@ -96,34 +99,34 @@ def test_gemm_lnx_vs_reference(hiplib, M, C, N, form, shift, cvariant):
         Wg, S, bf = _fold(W, gamma, beta, bias)
         nsamp = (M + rpf - 1) // rpf
         tab = torch.stack([bf + (W * pe[s % frames][None, :]).sum(dim=1) for s in range(nsamp)]).contiguous()
-        rowvec_t = tab.to(DEV)
+        rowvec_t = gvec(tab)
         rowvec_d, rps, epi = rowvec_t.data_ptr(), rpf, 2
         bias_d = 0
     else:
         ref = ln @ h16(W).t() + bias
         Wg, S, bf = _fold(W, gamma, beta, bias)
-        bias_t = bf.to(DEV)
+        bias_t = gvec(bf)
         bias_d = bias_t.data_ptr()
     n_out = N
     if form == "geglu":
         # hidden | gate halves; the library wants rows interleaved 16 | 16 (rcdm_pack_geglu_rows) — pack the FOLDED matrix
-        Wf32 = (W * gamma[None, :]).contiguous().to(DEV)
-        bf32 = bf.contiguous().to(DEV)
-        Wd = torch.empty(N, C, dtype=torch.float16, device=DEV)
-        bias_t = torch.empty(N, dtype=torch.float32, device=DEV)
+        Wf32 = gin((W * gamma[None, :]).contiguous())
+        bf32 = gvec(bf)
+        Wd = gout(N, C)
+        bias_t = gout(1, N, dtype=torch.float32, guard_rows=1)
         hip.pack_geglu_rows(Wf32.data_ptr(), bf32.data_ptr(), N, C, Wd.data_ptr(), bias_t.data_ptr())
         torch.cuda.synchronize()
-        Sd = Wd.float().sum(dim=1).contiguous()
+        Sd = gvec(Wd.float().sum(dim=1))
         bias_d, epi, n_out = bias_t.data_ptr(), 1 | 8, N // 2
         # reference: ln W^T with the UNFOLDED matrix (what the LayerNorm + GEGLU of the reference computes)
         full = ln @ W.t() + bias
         hid, gate = full[:, :N // 2], full[:, N // 2:]
         ref = hid * torch.nn.functional.gelu(gate)
     else:
-        Wd = Wg.to(DEV)
-        Sd = S.to(DEV)
+        Wd = gw(Wg)
+        Sd = gvec(S)
     ldc = n_out + 8
-    out = torch.full((M, ldc), float("nan"), dtype=torch.float16, device=DEV)
+    out = gout(M, n_out, ldc)
     hip.set_igemm_variant(cvariant)
     d = hip.GemmDesc(M, N, C, C, ldc, 0, epi, rps, N if form == "rowvec" else 0, 1.0, 1, 0)
     lx = hip.Lnx(0, 0, 0, stat.data_ptr(), parts, M, Sd.data_ptr(), 1e-5, C)
@@ -140,6 +143,7 @@ def test_gemm_lnx_vs_reference(hiplib, M, C, N, form, shift, cvariant):
     # against the LayerNorm -> Linear of the reference in fp32 (f16 storage of W and of the output are the only roundings
     # the separate-launch path has too; the deferred form adds the f16 staging of x W'^T before the mean term is removed)
     close(got, ref, rel=4e-3, abs_frac=6e-3)
+    check_all(out, x, Wd, Sd)
 
 
 @pytest.mark.parametrize("cvariant", [-1, 1, 5, 9, 10])
@@ -170,21 +174,21 @@ def test_gemm_lnx_rows_far_from_zero(hiplib, mean, sigma, form, cvariant):
     Wg, S, bf = _fold(W, gamma, beta, bias)
     assert (xs.abs().max() * S.abs().max()).item() > (3e3 if mean < 1e4 else 65504), "the case must stress the raw projection"
     if form == "geglu":
-        Wf32 = (W * gamma[None, :]).contiguous().to(DEV)
-        bf32 = bf.contiguous().to(DEV)
-        Wd = torch.empty(N, C, dtype=torch.float16, device=DEV)
-        bias_t = torch.empty(N, dtype=torch.float32, device=DEV)
+        Wf32 = gin((W * gamma[None, :]).contiguous())
+        bf32 = gvec(bf)
+        Wd = gout(N, C)
+        bias_t = gout(1, N, dtype=torch.float32, guard_rows=1)
         hip.pack_geglu_rows(Wf32.data_ptr(), bf32.data_ptr(), N, C, Wd.data_ptr(), bias_t.data_ptr())
         torch.cuda.synchronize()
-        Sd = Wd.float().sum(dim=1).contiguous()
+        Sd = gvec(Wd.float().sum(dim=1))
         epi, n_out = 1 | 8, N // 2
         full = ln @ W.t() + bias
         ref = full[:, :N // 2] * torch.nn.functional.gelu(full[:, N // 2:])
     else:
-        Wd, Sd, bias_t = Wg.to(DEV), S.to(DEV), bf.to(DEV)
+        Wd, Sd, bias_t = gw(Wg), gvec(S), gvec(bf)
         epi, n_out = 1, N
         ref = ln @ h16(W).t() + bias
-    out = torch.full((M, n_out), float("nan"), dtype=torch.float16, device=DEV)
+    out = gout(M, n_out)
     hip.set_igemm_variant(cvariant)
     d = hip.GemmDesc(M, N, C, C, n_out, 0, epi, 1, 0, 1.0, 1, 0)
     lx = hip.Lnx(0, 0, 0, stat.data_ptr(), parts, M, Sd.data_ptr(), 1e-5, C)
@@ -194,6 +198,7 @@ def test_gemm_lnx_rows_far_from_zero(hiplib, mean, sigma, form, cvariant):
     got = out.float().cpu()
     assert torch.isfinite(got).all(), "inf / NaN: a raw x W'^T value left the f16 range before the mean term was removed"
     close(got, ref, rel=8e-3, abs_frac=8e-3)
+    check_all(out, x, Wd, Sd, bias_t)
 
 
 def test_gemm_lnx_dup_rows_and_both_sides(hiplib):
@@ -216,9 +221,10 @@ def test_gemm_lnx_dup_rows_and_both_sides(hiplib):
     Wg, S, bf = _fold(W, gamma, beta, None)
     d = hip.GemmDesc(M, C, C, C, C, 0, 1, 1, 0, 1.0, 1, M)
     parts2 = hip.gemm_stat_parts(d)
-    out = torch.full((2 * M, C), float("nan"), dtype=torch.float16, device=DEV)
-    stat2 = torch.full((2 * M * parts2 * 2,), float("nan"), dtype=torch.float32, device=DEV)
-    Wd, Sd, bd = Wg.to(DEV), S.to(DEV), bf.to(DEV)
+    out = gout(2 * M, C)
+    stat2_h = gout(1, 2 * M * parts2 * 2, dtype=torch.float32, guard_rows=1)
+    stat2 = stat2_h[0]
+    Wd, Sd, bd = gw(Wg), gvec(S), gvec(bf)
     lx = hip.Lnx(stat2.data_ptr(), parts2, 2 * M, stat.data_ptr(), parts, 2 * M, Sd.data_ptr(), 1e-5, C)
     hip.gemm_lnx(d, lx, x.data_ptr(), Wd.data_ptr(), bd.data_ptr(), 0, 0, out.data_ptr(), 0, 0)
     torch.cuda.synchronize()
@@ -228,6 +234,7 @@ def test_gemm_lnx_dup_rows_and_both_sides(hiplib):
     assert torch.equal(o[:M], o[M:])
     s2 = stat2.cpu().view(parts2, 2 * M, 2).sum(dim=0)
     assert torch.allclose(s2[:M, 0], o[:M].sum(dim=1), rtol=1e-4, atol=1e-2) and torch.equal(s2[:M], s2[M:])
+    check_all(out, stat2_h, x, Wd, Sd, bd)
 
 
 def test_gemm_lnx_refusals(hiplib):
