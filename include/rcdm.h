@@ -48,6 +48,10 @@ extern "C" {
                              * the stage-1 prior (diffusers GELU(approximate="none")); not with GEGLU  */
 #define RCDM_EPI_GEGLU 8     /* out[m][j] = (h+bh) * gelu(g+bg); W/bias rows packed in groups of   */
                              /* 32 = 16 hidden rows then their 16 gate rows (rcdm_pack_geglu_rows) */
+#define RCDM_EPI_QUICK_GELU 32 /* out = v * sigmoid(1.702 v), v = acc + bias + rowvec (+ residual): transformers "quick_gelu", the
+                             * MLP activation of the SD-1.5 CLIP text encoder.  rcdm_gemm only (every tile family and the split-K
+                             * reduce); not with GELU / GEGLU (RCDM_EINVAL); rcdm_gemm_ln / _lnx / *_gnstat / rcdm_conv3x3*:
+                             * RCDM_ESHAPE */
 
 int rcdm_version(void);
 /* last HIP error code seen by this library on this thread (0 = none) and its string */
@@ -595,6 +599,19 @@ int rcdm_prior_assemble(const void* base, const float* temb, const float* latent
 int rcdm_cfg_unclip_step(const void* pred, int32_t ld, float* latents, int32_t n, int32_t reps, int32_t E,
                          float guidance_scale, float clip_range, const float* coef, const float* noise,
                          const int32_t* step_counter, void* stream);
+/* CLIP encoders (transformers CLIPTextModel / CLIPVisionModel, loaded at stage2_batchtest_rcdms_model.py:200-216 and called from
+ * RCDMs_pipeline.py:_encode_prompt / prior_pipeline.py), the two embedding layers in front of the transformer stacks.
+ * rcdm_embed_tokens: out[r][0..C) = f16(table[ids[r]][:] + pos[r % L][:]) for r < n_rows — CLIPTextEmbeddings.forward.  ids: device
+ *   int32 [n_rows]; table fp32 [vocab][C]; pos fp32 [>= L][C]; C % 8 == 0, ldo % 8 == 0 (16-byte stores).  The kernel does NOT
+ *   clamp: the caller guarantees 0 <= ids[r] < vocab.
+ * rcdm_patch_rows: the im2col of CLIPVisionEmbeddings.patch_embedding (Conv2d(3, C, patch, stride patch, bias=False)): pixels fp32
+ *   (B, 3, H, W) -> f16 rows [B * (P + 1)][ldk], P = (H / patch)(W / patch); row b (P + 1) is all zero (the class-token slot), row
+ *   b (P + 1) + 1 + p holds patch p flattened in the weight's own (c, ky, kx) order, columns 3 patch^2 .. ldk are zero.  One
+ *   rcdm_gemm against the zero-padded [C][ldk] weight with RCDM_EPI_RESIDUAL = the position table (+ class embedding in row 0)
+ *   is then the whole embedding.  H, W multiples of patch, ldk % 8 == 0, ldk >= 3 patch^2 (RCDM_ESHAPE otherwise). */
+int rcdm_embed_tokens(const int32_t* ids, int32_t n_rows, int32_t L, const float* table, int32_t vocab, const float* pos,
+                      int32_t C, void* out, int32_t ldo, void* stream);
+int rcdm_patch_rows(const float* pixels, int32_t B, int32_t H, int32_t W, int32_t patch, void* out, int32_t ldk, void* stream);
 /* t_out[0..rows) = timesteps[*step_counter] (fp32) — feeds rcdm_timestep_embed inside a graph */
 int rcdm_load_timestep(const float* timesteps, const int32_t* step_counter, float* t_out,
                        int32_t rows, void* stream);

@@ -871,6 +871,13 @@ int rcdm_flash_attn_masked(const rcdm_attn_desc* d, const void* Q, const void* K
   if (ds <= 2) return launch_flash<2>(a, stream);
   if (ds <= 3) return launch_flash<3>(a, stream);
   if (ds <= 5) return launch_flash<5>(a, stream);
+  // 80 < d <= 112 (the 104-wide heads of the CLIP-bigG vision tower): QK^T padded to 112 and PV to 128 instead of 160 / 160
+  static int ds7_mode = -1;  // RCDM_ATTN_DS7=0: the 160-wide form for these heads too (A/B switch)
+  if (ds7_mode < 0) {
+    const char* e = getenv("RCDM_ATTN_DS7");
+    ds7_mode = e ? atoi(e) : 1;
+  }
+  if (ds7_mode && (ds == 6 || ds == 7)) return launch_flash<7>(a, stream);
   return launch_flash<10>(a, stream);
 }
 

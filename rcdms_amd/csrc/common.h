@@ -89,6 +89,29 @@ __device__ __forceinline__ void gelu8(float (&v)[8]) {
     v[2 * k + 1] = r.y;
   }
 }
+// quick-GELU (transformers "quick_gelu", RCDM_EPI_QUICK_GELU): x * sigmoid(1.702 x), written in the shape of gelu2 —
+// max(x, 0) - |x| q with q = sigmoid(-1.702 |x|) = 1 / (1 + 2^(1.702 log2(e) |x|)): v_exp_f32 and v_rcp_f32, 1 ulp each;
+// |x| large: 2^big = inf, q = 0.
+__device__ __forceinline__ f32x2 quick_gelu2(f32x2 x) {
+  const f32x2 ax = __builtin_elementwise_abs(x);
+  const f32x2 z = ax * splat2(2.45548296f);
+  const f32x2 d = {1.0f + __builtin_amdgcn_exp2f(z.x), 1.0f + __builtin_amdgcn_exp2f(z.y)};
+  const f32x2 q = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+  return __builtin_elementwise_fma(-ax, q, __builtin_elementwise_max(x, splat2(0.0f)));
+}
+__device__ __forceinline__ void quick_gelu8(float (&v)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f32x2 r = quick_gelu2(f32x2{v[2 * k], v[2 * k + 1]});
+    v[2 * k] = r.x;
+    v[2 * k + 1] = r.y;
+  }
+}
+// the activation of a GELU-family epilogue: quick != 0 (wave-uniform) the sigmoid form, else the erf form
+__device__ __forceinline__ void act8(float (&v)[8], int quick) {
+  if (quick) quick_gelu8(v);
+  else gelu8(v);
+}
 // GEGLU on eight packed halfs: (h + bh) * gelu(g + bg) * sc -> eight halfs
 __device__ __forceinline__ uint4 geglu8(uint4 h, uint4 g, const float (&bh)[8], const float (&bg)[8], float sc) {
   union P { uint4 u; f16 e[8]; } hh, gg, o;

@@ -61,6 +61,7 @@ __device__ __forceinline__ void slab_add8(const IgemmArgs& p, size_t off, float 
   }
 }
 
+template <bool QG = false>   // QG: the quick-GELU form compiled in (its own reduce kernel: the existing ones keep their code)
 __device__ __forceinline__ uint4 epilogue_store(const IgemmArgs& p, int m, int n, float (&v)[8], float (&g)[8]) {   // returns the 8 halfs it stored
   int oc = n;
   if (p.epi & RCDM_EPI_GEGLU) {
@@ -89,6 +90,9 @@ __device__ __forceinline__ uint4 epilogue_store(const IgemmArgs& p, int m, int n
     load8(p.rowvec + (size_t)(m / p.rows_per_sample) * p.ldt + oc, rv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] += rv[e];
+  }
+  if constexpr (QG) {
+    if (p.epi & RCDM_EPI_QUICK_GELU) quick_gelu8(v);
   }
   if (p.epi & RCDM_EPI_GELU) gelu8(v);
   if (p.epi & RCDM_EPI_RESIDUAL) {
@@ -134,7 +138,7 @@ constexpr int TRACE_SLOTS = 4;
 #endif
 #endif
 
-template <int TAPS, int BM_, int BN_, int WM, int WN, int NSTAGE, bool E16, int LX = 0>  // LX: deferred-LayerNorm epilogues (rcdm_gemm_lnx) compiled in: 1 = row statistics only, 2 = consumer (+ statistics)
+template <int TAPS, int BM_, int BN_, int WM, int WN, int NSTAGE, bool E16, int LX = 0>  // LX: deferred-LayerNorm epilogues (rcdm_gemm_lnx) compiled in: 1 = row statistics only, 2 = consumer (+ statistics); 4 = the quick-GELU epilogue instead (RCDM_EPI_QUICK_GELU launches only: every other instantiation keeps its code and registers)
 // (second launch bound = waves per SIMD the tile's LDS footprint allows: 4 blocks of 64x64, 3 of 128x64, 2 of 128x128 per CU)
 #ifdef RCDM_DMA_MINW2   // A/B builds: the round-3 bound (2 waves per SIMD for every tile)
 #define RCDM_DMA_MINW(wm, wn, bm, bn, ns) 2
@@ -497,7 +501,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
       // deferred LayerNorm of the A rows (rcdm_gemm_lnx): LTPR threads per tile row sum that row's partial statistics;
       // (rstd, mean rstd) go to a [BM][2] table behind the ring, published by the staging barrier of the first pass
       constexpr bool lnx = LXC;
-      const bool stat_on = LX != 0 && p.stat_out != nullptr && !(RCDM_LNX_ABLATE & 256);
+      const bool stat_on = (LX & 3) != 0 && p.stat_out != nullptr && !(RCDM_LNX_ABLATE & 256);
       const int stat_tn = cn0 / BN_;
       const int dup_rows = p.dup ? (int)(p.dup / p.ldc) : 0;
       if (WHOLE && !geglu) {
@@ -574,7 +578,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
               }
           }
         } else {
-          const bool gelu_on = (p.epi & RCDM_EPI_GELU) != 0;
+          const bool gelu_on = (p.epi & (RCDM_EPI_GELU | ((LX & 4) ? RCDM_EPI_QUICK_GELU : 0))) != 0;
           float cA[8], cB[8];  // (bias + row vector) * scale of the tile's first / second sample
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
@@ -620,6 +624,8 @@ void igemm_dma_kernel(const IgemmArgs p) {
                       for (int e = 0; e < 8; ++e) v[e] += rv[e];
                     }
                     if (gelu_on) {
+                      if constexpr ((LX & 4) != 0) quick_gelu8(v);
+                      else
                       gelu8(v);
                     }
 #pragma unroll
@@ -758,6 +764,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
 }
 
 // split-K second pass: fixed-order sum of the fp32 slabs + the epilogue (8 output columns per thread).
+template <bool QG>   // QG: RCDM_EPI_QUICK_GELU launches
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmArgs p) {
   const bool geglu = (p.epi & RCDM_EPI_GEGLU) != 0;
   const int nout8 = (geglu ? p.N / 2 : p.N) / 8;
@@ -775,7 +782,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmArgs p) {
       slab_add8(p, off, v);
       if (geglu) slab_add8(p, off + kGegluGroup, g);
     }
-    epilogue_store(p, p.ph_rows ? phase_out_row(p, m) : m, n, v, g);   // (phase launches carry a bias at most: no per-row operand)
+    epilogue_store<QG>(p, p.ph_rows ? phase_out_row(p, m) : m, n, v, g);   // (phase launches carry a bias at most: no per-row operand)
   }
 }
 
@@ -869,7 +876,8 @@ int launch_splitk_reduce(const IgemmArgs& a, hipStream_t stream) {
   const size_t total = (size_t)a.M * ((geglu ? a.N / 2 : a.N) / 8);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, a);
+  if (a.epi & RCDM_EPI_QUICK_GELU) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, stream, a);
   return rcdm_check_launch();
 }
 
@@ -1149,7 +1157,8 @@ int fill_common(IgemmArgs& a, int requested_split, int* variant_out = nullptr, i
   int variant = forced_variant >= 0 ? forced_variant : pick_variant(a);
   // the 256x256 LDS-DMA tile is at the 256-register cap: its statistics / deferred-LayerNorm instantiations spilled (12 /
   // 200 B of scratch) and are not built — such launches take the 128x128 tile, also when variant 2 is forced
-  if (variant == 2 && (a.stat_out || a.lnx_stat)) variant = 1;
+  // (so did its quick-GELU instantiation, 8 B: the same rule)
+  if (variant == 2 && (a.stat_out || a.lnx_stat || (a.epi & RCDM_EPI_QUICK_GELU))) variant = 1;
   if (variant_out) *variant_out = variant;
   const TileCfg& tc = kTiles[variant];
   a.tilesM = (a.M + tc.bm - 1) / tc.bm;
@@ -1197,6 +1206,7 @@ int check_common(const IgemmArgs& a) {
   if ((a.epi & RCDM_EPI_RESIDUAL) && (!a.res || (a.ldr & 7))) return RCDM_EINVAL;
   if ((a.epi & RCDM_EPI_GEGLU) && (a.N % 32)) return RCDM_ESHAPE;
   if ((a.epi & RCDM_EPI_GEGLU) && (a.epi & RCDM_EPI_GELU)) return RCDM_EINVAL;
+  if ((a.epi & RCDM_EPI_QUICK_GELU) && (a.epi & (RCDM_EPI_GELU | RCDM_EPI_GEGLU))) return RCDM_EINVAL;
   if (a.dup < 0) return RCDM_EINVAL;
   // buffer-load offsets are 32-bit with 0x80000000 reserved as "out of range"
   const size_t in_rows = (a.Ktot == a.Cin) ? (size_t)a.M : (size_t)(a.M / (a.Ho * a.Wo)) * a.Hi * a.Wi;
@@ -1235,7 +1245,8 @@ int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, h
       set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, false>, LDS);                        \
       set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true>, LDS);                         \
       set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 1>, LDS);                      \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 2>, LDS)
+      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 2>, LDS);                      \
+      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 4>, LDS)
       RCDM_DEEP_LDS(128, 64, 3, LDS_128x64_3);
 #undef RCDM_DEEP_LDS
       set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true, 1>, LDS_128);
@@ -1246,6 +1257,10 @@ int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, h
       set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true, 2>, LDS_64);
       set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true, 2>, LDS_64D);
       set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true, 2>, LDS_128x64);
+      set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true, 4>, LDS_128);
+      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true, 4>, LDS_64);
+      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true, 4>, LDS_64D);
+      set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true, 4>, LDS_128x64);
     }
   }
   if (a.splits > 1) {
@@ -1314,6 +1329,10 @@ int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, h
         hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true, 1>), grid, dim3(THREADS), LDS, stream, a); \
         break;                                                                                                        \
       }                                                                                                               \
+      if (e16 && (a.epi & RCDM_EPI_QUICK_GELU)) {                                                                     \
+        hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true, 4>), grid, dim3(THREADS), LDS, stream, a); \
+        break;                                                                                                        \
+      }                                                                                                               \
     }                                                                                                                 \
     if (e16) hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true>), grid, dim3(THREADS), LDS, stream, a); \
     else hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, false>), grid, dim3(THREADS), LDS, stream, a);    \
@@ -1344,6 +1363,7 @@ int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, h
 // form, and the epilogue has no GEGLU / second row copy / phase rows.  With gn_ws: also points a.gn_partial into it.
 int attach_gnstat(IgemmArgs& a, const rcdm_groupnorm_desc* gn, void* gn_ws, size_t gn_ws_bytes, bool need_ws) {
   if (!gn) return RCDM_EINVAL;
+  if (a.epi & RCDM_EPI_QUICK_GELU) return RCDM_ESHAPE;   // (the encoders' activation: plain rcdm_gemm only)
   if (a.splits <= 1 || (a.epi & RCDM_EPI_GEGLU) || a.dup || a.ph_rows) return RCDM_ESHAPE;
   GnArgs g{};
   int rc = rcdm_gn_plan(gn, g);
@@ -1455,7 +1475,7 @@ int conv_launch(const rcdm_conv3x3_desc* d, const rcdm_groupnorm_desc* gn, const
   a.A2 = (const f16*)in2;
   rc = check_common(a);
   if (rc) return rc;
-  if (a.epi & RCDM_EPI_GEGLU) return RCDM_ESHAPE;
+  if (a.epi & (RCDM_EPI_GEGLU | RCDM_EPI_QUICK_GELU)) return RCDM_ESHAPE;
   int variant = 0;
   fill_common(a, d->split_k, &variant);
   if (gn) {
@@ -1590,6 +1610,7 @@ int rcdm_gemm_lnx(const rcdm_gemm_desc* d, const rcdm_lnx* x, const void* A, con
   a.res = (const f16*)residual; a.out = (f16*)out;
   int rc = check_common(a);
   if (rc) return rc;
+  if (a.epi & RCDM_EPI_QUICK_GELU) return RCDM_ESHAPE;
   if (x->stat_out) {
     if (x->stat_parts <= 0 || ((uintptr_t)x->stat_out & 7)) return RCDM_EINVAL;
     a.stat_out = x->stat_out;
@@ -1637,7 +1658,7 @@ int rcdm_gemm_ln(const rcdm_gemm_desc* d, const rcdm_ln_fuse* ln, const void* A,
   if (rc) return rc;
   // one 160x320 ping-pong tile must span the output row; only the plain epilogues
   if (a.N > kPPShapes[0].bn || (ln->ld & 7) || d->split_k > 1) return RCDM_ESHAPE;
-  if (a.epi & (RCDM_EPI_GEGLU | RCDM_EPI_GELU | RCDM_EPI_ROWVEC)) return RCDM_ESHAPE;
+  if (a.epi & (RCDM_EPI_GEGLU | RCDM_EPI_GELU | RCDM_EPI_QUICK_GELU | RCDM_EPI_ROWVEC)) return RCDM_ESHAPE;
   a.tilesM = (a.M + kPPShapes[0].bm - 1) / kPPShapes[0].bm;
   a.tilesN = 1;
   a.kc = (a.Cin + BK - 1) / BK;
@@ -1687,7 +1708,7 @@ int rcdm_conv3x3(const rcdm_conv3x3_desc* d, const void* in, const void* W, cons
     const size_t total = (size_t)a.M * (a.N / 8);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return rcdm_check_launch();
   }
   return conv_launch(d, nullptr, in, nullptr, W, bias, rowvec, residual, out, workspace, workspace_bytes, nullptr, 0, stream);

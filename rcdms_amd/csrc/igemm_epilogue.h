@@ -380,7 +380,11 @@ __device__ __forceinline__ void tile_epilogue(const IgemmArgs& p, char* stg, f32
                 v[4 + e] += a1[e];
               }
             }
-            if (epi & RCDM_EPI_GELU) gelu8(v);
+            if constexpr (LN_OK || LX) {   // (either flag: a GEMM launch, TAPS == 1 — the only ones that can carry the quick form)
+              if (epi & (RCDM_EPI_GELU | RCDM_EPI_QUICK_GELU)) act8(v, epi & RCDM_EPI_QUICK_GELU);
+            } else {
+              if (epi & RCDM_EPI_GELU) gelu8(v);
+            }
             Pack16 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o.e[e] = (f16)((v[e] + (float)rr[u].e[e]) * sc);

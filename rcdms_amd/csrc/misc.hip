@@ -264,6 +264,56 @@ __global__ void prior_assemble_kernel(const f16* __restrict__ base, const float*
   }
 }
 
+// CLIP text embeddings (transformers CLIPTextEmbeddings.forward): row r <- f16(token_embedding[ids[r]] + position_embedding[r % L]),
+// one 16-byte store per thread.  The ids are trusted (the caller range-checks them on the host).
+__global__ void embed_tokens_kernel(const int* __restrict__ ids, int n_rows, int L, const float* __restrict__ table,
+                                    const float* __restrict__ pos, int C, f16* __restrict__ out, int ldo) {
+  const int cpr = C / 8;
+  const size_t chunks = (size_t)n_rows * cpr;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < chunks; i += (size_t)gridDim.x * blockDim.x) {
+    const int c8 = (int)(i % cpr);
+    const size_t r = i / cpr;
+    const float* t = table + (size_t)ids[r] * C + c8 * 8;
+    const float* q = pos + (size_t)(r % L) * C + c8 * 8;
+    const f32x4 t0 = *(const f32x4*)t, t1 = *(const f32x4*)(t + 4), q0 = *(const f32x4*)q, q1 = *(const f32x4*)(q + 4);
+    Pack16 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v.e[e] = (f16)(t0[e] + q0[e]);
+      v.e[4 + e] = (f16)(t1[e] + q1[e]);
+    }
+    *(uint4*)(out + r * ldo + c8 * 8) = v.u;
+  }
+}
+
+// CLIP vision patch embedding as GEMM rows (transformers CLIPVisionEmbeddings.forward: Conv2d(3, C, patch, stride patch,
+// bias=False) then the class token in front): image b gives Ph Pw + 1 rows of ldk halfs — row 0 all zero (the class-token slot:
+// the GEMM leaves its residual operand there), row 1 + p the pixels of patch p in the weight's (c, ky, kx) order, columns
+// 3 patch^2 .. ldk zero.
+__global__ void patch_rows_kernel(const float* __restrict__ px, int B, int H, int W, int patch, f16* __restrict__ out, int ldk) {
+  const int Pw = W / patch, T = (H / patch) * Pw + 1, cpr = ldk / 8, pp = patch * patch, K = 3 * pp;
+  const size_t chunks = (size_t)B * T * cpr;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < chunks; i += (size_t)gridDim.x * blockDim.x) {
+    const int c8 = (int)(i % cpr);
+    const size_t row = i / cpr;
+    const int b = (int)(row / T), j = (int)(row % T);
+    Pack16 v;
+    v.u = make_uint4(0, 0, 0, 0);
+    if (j > 0) {
+      const int py = (j - 1) / Pw, pxx = (j - 1) % Pw;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int col = c8 * 8 + e;
+        if (col < K) {
+          const int c = col / pp, k = col - c * pp, ky = k / patch, kx = k - ky * patch;
+          v.e[e] = (f16)px[(((size_t)b * 3 + c) * H + py * patch + ky) * W + pxx * patch + kx];
+        }
+      }
+    }
+    *(uint4*)(out + row * ldk + c8 * 8) = v.u;
+  }
+}
+
 // Stage-1 prior, CFG combine + UnCLIPScheduler.step (prediction_type "sample", variance_type "fixed_small_log"),
 // prior_pipeline.py:328-344 + diffusers 0.24.0 UnCLIPScheduler.step: x0 = clamp(u + s (c - u), +-clip);
 // lat = k0 x0 + k1 lat + k2 noise, with (k0, k1, k2) = coef[*step] (k2 = 0 on the last step).
@@ -492,6 +542,26 @@ int rcdm_prior_assemble(const void* base, const float* temb, const float* latent
   const size_t n = (size_t)B * L * (C / 8) + (size_t)B * E;
   hipLaunchKernelGGL(prior_assemble_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const f16*)base, temb,
                      latents, n_lat, (f16*)tok, (f16*)x16, B, L, C, E, time_row);
+  return rcdm_check_launch();
+}
+
+int rcdm_embed_tokens(const int32_t* ids, int32_t n_rows, int32_t L, const float* table, int32_t vocab, const float* pos,
+                      int32_t C, void* out, int32_t ldo, void* stream) {
+  if (!ids || !table || !pos || !out) return RCDM_EINVAL;
+  if (n_rows <= 0 || L <= 0 || vocab <= 0 || C <= 0) return RCDM_EINVAL;
+  if ((C & 7) || (ldo & 7) || ldo < C) return RCDM_ESHAPE;
+  const size_t n = (size_t)n_rows * (C / 8);
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, ids, n_rows, L, table, pos, C,
+                     (f16*)out, ldo);
+  return rcdm_check_launch();
+}
+
+int rcdm_patch_rows(const float* pixels, int32_t B, int32_t H, int32_t W, int32_t patch, void* out, int32_t ldk, void* stream) {
+  if (!pixels || !out || B <= 0 || H <= 0 || W <= 0 || patch <= 0) return RCDM_EINVAL;
+  if ((H % patch) || (W % patch) || (ldk & 7) || ldk < 3 * patch * patch) return RCDM_ESHAPE;
+  const size_t n = (size_t)B * ((H / patch) * (W / patch) + 1) * (ldk / 8);
+  hipLaunchKernelGGL(patch_rows_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, pixels, B, H, W, patch, (f16*)out,
+                     ldk);
   return rcdm_check_launch();
 }
 

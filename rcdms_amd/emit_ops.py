@@ -34,7 +34,7 @@ def assert_no_pending_gn(plan, who):
 
 
 def emit_gemm(plan, A, Wt, N, K, out, bias=None, rowvec=None, residual=None, geglu=False, scale=1.0, split_k=0,
-              gelu=False, dup_rows=0, stat=False, lnx=None, gn=None, stat_into=None, stat_row0=0):
+              gelu=False, dup_rows=0, stat=False, lnx=None, gn=None, stat_into=None, stat_row0=0, quick_gelu=False):
     """out[M][N or N/2] = epi(A[M][K] W[N][K]^T); rowvec = (tensor, elem_offset, ldt, rows_per_sample).
     Deferred LayerNorm (rcdm_gemm_lnx): stat=True — also write the row statistics of the stored rows and RETURN their handle
     (None when this shape has no statistics-producing launch: the caller then emits the stand-alone LayerNorm);
@@ -54,6 +54,9 @@ def emit_gemm(plan, A, Wt, N, K, out, bias=None, rowvec=None, residual=None, geg
         epi |= hip.EPI_GEGLU
     if gelu:
         epi |= hip.EPI_GELU
+    if quick_gelu:      # x * sigmoid(1.702 x): the CLIP text encoder's MLP (plain rcdm_gemm launches only)
+        assert not (gelu or geglu or stat or lnx is not None or gn is not None or stat_into is not None)
+        epi |= hip.EPI_QUICK_GELU
     d = hip.GemmDesc(A.M, N, K, A.ld, out.ld, residual.ld if residual is not None else 0, epi,
                      rowvec[3] if rowvec else 1, rowvec[2] if rowvec else 0, scale, split_k, dup_rows)
     handle, x = None, None
@@ -307,8 +310,8 @@ def emit_conv3x3_wino(plan, x, n_img, H, W, U, cin, cout, out, bias=None, rowvec
     plan.n_launch += 3
 
 
-def emit_layernorm(plan, x, gamma, beta, out, pe=None, rows_per_frame=1, frames=1):
-    d = hip.LayerNormDesc(x.M, x.C, x.ld, out.ld, 1e-5, rows_per_frame, frames)
+def emit_layernorm(plan, x, gamma, beta, out, pe=None, rows_per_frame=1, frames=1, eps=1e-5):
+    d = hip.LayerNormDesc(x.M, x.C, x.ld, out.ld, eps, rows_per_frame, frames)
 
     def op():
         hip.layernorm(d, x.ptr, gamma.data_ptr(), beta.data_ptr(), pe.data_ptr() if pe is not None else 0, out.ptr)
@@ -356,9 +359,10 @@ def emit_xattn(plan, q, img, batch, heads, Lq, Lk, d_head, out):
     plan.n_launch += 1
 
 
-def emit_flash_attn_masked(plan, q, k, v, batch, heads, Lq, Lk, d_head, out, key_valid, causal):
-    """key_valid: uint8 tensor [batch][Lk] (or None); causal: bool or a callable evaluated at launch time."""
-    d = hip.AttnDesc(batch, heads, Lq, Lk, d_head, q.ld, k.ld, v.ld, out.ld, d_head ** -0.5)
+def emit_flash_attn_masked(plan, q, k, v, batch, heads, Lq, Lk, d_head, out, key_valid, causal, wide=False):
+    """key_valid: uint8 tensor [batch][Lk] (or None); causal: bool or a callable evaluated at launch time; wide: as
+    emit_flash_attn."""
+    d = hip.AttnDesc(batch, heads, Lq, Lk, d_head, q.ld, k.ld, v.ld, out.ld, d_head ** -0.5, hip.ATTN_WIDE_RANGE if wide else 0)
 
     def op():
         c = causal() if callable(causal) else causal

@@ -10,7 +10,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RCDM_LIB") or os.path.join(_HERE, "lib", "librcdm_hip.so")  # RCDM_LIB: kernel experiments
 
-EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU, EPI_GELU = 1, 2, 4, 8, 16
+EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU, EPI_GELU, EPI_QUICK_GELU = 1, 2, 4, 8, 16, 32
 
 _ERR = {-1: "RCDM_EINVAL", -2: "RCDM_ESHAPE", -3: "RCDM_ELAUNCH", -4: "RCDM_EWORKSPACE", -5: "RCDM_ECOMM"}
 
@@ -142,6 +142,8 @@ SYMBOLS = {
     "rcdm_cfg_sigma_step": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "rcdm_prior_assemble": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rcdm_cfg_unclip_step": (C.c_int, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "rcdm_embed_tokens": (C.c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
+    "rcdm_patch_rows": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _P]),
     "rcdm_load_timestep": (C.c_int, [_P, _P, _P, _I, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
@@ -444,6 +446,16 @@ def prior_assemble(base, temb, latents, n_lat, tok, x16, B, L, Cc, E, time_row, 
 def cfg_unclip_step(pred, ld, latents, n, reps, E, guidance_scale, clip_range, coef, noise, step_counter, stream=None):
     _check(load().rcdm_cfg_unclip_step(pred, ld, latents, n, reps, E, guidance_scale, clip_range, coef, noise,
                                        step_counter, stream_ptr() if stream is None else stream), "rcdm_cfg_unclip_step")
+
+
+def embed_tokens(ids, n_rows, L, table, vocab, pos, Cc, out, ldo, stream=None):
+    _check(load().rcdm_embed_tokens(ids, n_rows, L, table, vocab, pos, Cc, out, ldo,
+                                    stream_ptr() if stream is None else stream), "rcdm_embed_tokens")
+
+
+def patch_rows(pixels, B, H, W, patch, out, ldk, stream=None):
+    _check(load().rcdm_patch_rows(pixels, B, H, W, patch, out, ldk, stream_ptr() if stream is None else stream),
+           "rcdm_patch_rows")
 
 
 def assemble_input(lat, mask, masked, S, reps, frames, H, W, out, ld, c_pad, stream=None):
