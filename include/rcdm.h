@@ -648,6 +648,68 @@ int rcdm_pack_geglu_rows(const float* w, const float* bias, int32_t n_out /*8C*/
 int rcdm_mish(const float* x, float* y, size_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Images: uint8 frames in, uint8 frames out.
+ *
+ * rcdm_image_resample: Pillow's ImagingResample for 8-bit channels, the arithmetic under the driver's two preprocessors
+ *   (stage2_batchtest_rcdms_model.py:172-196,255-276: CLIPImageProcessor's bicubic shortest-edge resize + centre crop +
+ *   rescale + normalise, and ToPILImage -> Resize -> ToTensor -> Normalize(0.5, 0.5)), bit for bit: one launch resamples
+ *   n equally sized HWC images, horizontal pass first (rounded to uint8), vertical pass over it; the intermediate image
+ *   lives in LDS only.  The caller builds the integer tables (Pillow's precompute_coeffs + normalize_coeffs_8bpc, in double):
+ *     kx int32 [out_w][taps_x]  coefficients of output column x, 22 fractional bits, entries past the count unused
+ *     bx int32 [out_w][2]       (first source column, count <= taps_x) of output column x
+ *     ky / by                   the same for rows.
+ *   One pass per axis: acc = 2^21 + sum_i pix[first + i] * k[i] in int32, out = clamp(acc >> 22, 0, 255).  An axis Pillow
+ *   skips (size kept, no box) is the table (k = 2^22, count 1), which is the identity.  A crop after the resize is a table
+ *   that holds only the rows / columns inside the crop window: out_h x out_w is the window.  The kernel clamps every table
+ *   entry to the source image, so a wrong table gives wrong pixels, never an access outside `src`.
+ *   tile_rows: the largest number of source rows (max(first + count) - min(first)) that the output rows of one
+ *   RCDM_IMAGE_TILE-row tile (rows t * TILE .. t * TILE + TILE - 1) read; sizes the LDS of the launch
+ *   (rcdm_image_resample_lds_bytes: 0 for a descriptor the entry point would refuse; more than 64 KiB is RCDM_ESHAPE).
+ *   Output modes, channel c of the output = channel (flip_channels ? 2 - c : c) of the source (BGR <-> RGB):
+ *     RCDM_IMAGE_U8        uint8 HWC, dst_pitch / dst_stride bytes per row / per image
+ *     RCDM_IMAGE_F32_NCHW  fp32 (n, 3, out_h, out_w) dense: (u8 * (1/255) - mean[c]) * (1 / std[c]), every step rounded to fp32
+ *     RCDM_IMAGE_F16_ROWS  f16 pixel rows [n * out_h * out_w][ld] (the activation layout above): the fp32 value of
+ *                          RCDM_IMAGE_F32_NCHW rounded once to f16 in channels 0..2, zeros in channels 3..c_pad
+ *                          (c_pad % 8 == 0, ld % 8 == 0, ld >= c_pad >= 8, dst 16-byte aligned).
+ *   Limits (RCDM_ESHAPE): channels == 3, taps <= 40 per axis (an 8x bicubic reduction), sides <= 8192, n <= 65535.  Null
+ *   pointers, a pitch below 3 * width, an unknown mode, std <= 0: RCDM_EINVAL.  All checked before anything is launched.
+ * rcdm_frames_to_u8: the back end, RCDMs_pipeline.py:274-287 + the driver's (x * 255).astype(uint8):
+ *   u8 = trunc(clamp(x * 0.5 + 0.5, 0, 1) * 255) in fp32 (the product by 255 rounded on its own; NaN -> 0) from either the VAE
+ *   decoder's f16 pixel rows [n * H * W][ld] (ld >= 3, channels 0..2) or an fp32 (n, 3, H, W) tensor, to uint8 HWC at
+ *   dst + image * dst_stride + y * dst_pitch + 3 x: with dst_stride = 3 W and dst_pitch = the pitch of a grid image the n
+ *   frames land side by side in one row of cells.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_IMAGE_TILE 32
+#define RCDM_IMAGE_U8 0
+#define RCDM_IMAGE_F32_NCHW 1
+#define RCDM_IMAGE_F16_ROWS 2
+typedef struct {
+  int64_t src_pitch, src_stride;   /* bytes between source rows / source images */
+  int64_t dst_pitch, dst_stride;   /* RCDM_IMAGE_U8: bytes between output rows / output images */
+  int32_t n, channels;
+  int32_t in_h, in_w, out_h, out_w;
+  int32_t taps_x, taps_y;          /* row length of kx / ky */
+  int32_t tile_rows;
+  int32_t flip_channels;
+  int32_t mode;                    /* RCDM_IMAGE_* */
+  int32_t ld, c_pad;               /* RCDM_IMAGE_F16_ROWS */
+  float mean[3], std[3];           /* RCDM_IMAGE_F32_NCHW / _F16_ROWS, per OUTPUT channel */
+} rcdm_resample_desc;
+size_t rcdm_image_resample_lds_bytes(const rcdm_resample_desc* d);
+int rcdm_image_resample(const rcdm_resample_desc* d, const void* src, const int32_t* kx, const int32_t* bx, const int32_t* ky,
+                        const int32_t* by, void* dst, void* stream);
+
+#define RCDM_FRAMES_F16_ROWS 0
+#define RCDM_FRAMES_F32_NCHW 1
+typedef struct {
+  int64_t dst_pitch, dst_stride;   /* bytes between output rows / output images */
+  int32_t n, H, W, channels;       /* channels == 3 */
+  int32_t src_kind;                /* RCDM_FRAMES_* */
+  int32_t ld;                      /* RCDM_FRAMES_F16_ROWS: row stride in elements */
+} rcdm_frames_u8_desc;
+int rcdm_frames_to_u8(const rcdm_frames_u8_desc* d, const void* src, void* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

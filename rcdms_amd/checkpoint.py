@@ -76,11 +76,18 @@ def split_list(n, m):
 
 
 def image_grid(imgs, rows, cols):
-    """rows x cols PNG grid of float images in [0, 1], H x W x 3 each (:79-93; values are truncated to uint8 as there)."""
+    """rows x cols PNG grid of float images in [0, 1], H x W x 3 each (:79-93; values are truncated to uint8 as there).
+    uint8 tiles (numpy or tensors: the frames of `output_type="uint8"` / rcdms_amd.image.frames_to_uint8) are pasted as they are."""
     from PIL import Image
     if len(imgs) != rows * cols:
         raise AssertionError(f"{len(imgs)} images do not fill a {rows} x {cols} grid")
-    tiles = [Image.fromarray((np.array(im) * 255).astype(np.uint8)) for im in imgs]
+
+    def tile(im):
+        if isinstance(im, torch.Tensor) and im.dtype == torch.uint8:
+            im = im.detach().cpu().numpy()
+        a = np.array(im)
+        return Image.fromarray(a if a.dtype == np.uint8 else (a * 255).astype(np.uint8))
+    tiles = [tile(im) for im in imgs]
     w, h = tiles[0].size
     grid = Image.new("RGB", size=(cols * w, rows * h))
     for i, t in enumerate(tiles):

@@ -81,6 +81,23 @@ class TemporalAttnDesc(C.Structure):
                 ("scale", C.c_float)]
 
 
+class ResampleDesc(C.Structure):
+    _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("dst_pitch", C.c_int64), ("dst_stride", C.c_int64),
+                ("n", C.c_int32), ("channels", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("taps_x", C.c_int32), ("taps_y", C.c_int32),
+                ("tile_rows", C.c_int32), ("flip_channels", C.c_int32), ("mode", C.c_int32), ("ld", C.c_int32),
+                ("c_pad", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+class FramesU8Desc(C.Structure):
+    _fields_ = [("dst_pitch", C.c_int64), ("dst_stride", C.c_int64), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("channels", C.c_int32), ("src_kind", C.c_int32), ("ld", C.c_int32)]
+
+
+IMAGE_TILE = 32                                         # RCDM_IMAGE_TILE
+IMAGE_U8, IMAGE_F32_NCHW, IMAGE_F16_ROWS = 0, 1, 2      # ResampleDesc.mode
+FRAMES_F16_ROWS, FRAMES_F32_NCHW = 0, 1                 # FramesU8Desc.src_kind
+
 # every symbol include/rcdm.h declares: name -> (restype, argtypes)
 _P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -145,6 +162,9 @@ SYMBOLS = {
     "rcdm_embed_tokens": (C.c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "rcdm_patch_rows": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _P]),
     "rcdm_load_timestep": (C.c_int, [_P, _P, _P, _I, _P]),
+    "rcdm_image_resample_lds_bytes": (_SZ, [C.POINTER(ResampleDesc)]),
+    "rcdm_image_resample": (C.c_int, [C.POINTER(ResampleDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "rcdm_frames_to_u8": (C.c_int, [C.POINTER(FramesU8Desc), _P, _P, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -456,6 +476,19 @@ def embed_tokens(ids, n_rows, L, table, vocab, pos, Cc, out, ldo, stream=None):
 def patch_rows(pixels, B, H, W, patch, out, ldk, stream=None):
     _check(load().rcdm_patch_rows(pixels, B, H, W, patch, out, ldk, stream_ptr() if stream is None else stream),
            "rcdm_patch_rows")
+
+
+def image_resample_lds_bytes(desc):
+    return int(load().rcdm_image_resample_lds_bytes(C.byref(desc)))
+
+
+def image_resample(desc, src, kx, bx, ky, by, dst, stream=None):
+    _check(load().rcdm_image_resample(C.byref(desc), src, kx, bx, ky, by, dst, stream_ptr() if stream is None else stream),
+           "rcdm_image_resample")
+
+
+def frames_to_u8(desc, src, dst, stream=None):
+    _check(load().rcdm_frames_to_u8(C.byref(desc), src, dst, stream_ptr() if stream is None else stream), "rcdm_frames_to_u8")
 
 
 def assemble_input(lat, mask, masked, S, reps, frames, H, W, out, ld, c_pad, stream=None):

@@ -136,14 +136,26 @@ class AutoencoderKLDecoder(nn.Module):
     def decode(self, z, return_dict=True):
         if self.device.type != "cuda":
             raise hip.RcdmError(f"AutoencoderKLDecoder runs on the HIP path only (module is on {self.device})")
+        out = self._decode_program(z).forward(z).to(z.dtype)
+        return _Sample(out) if return_dict else (out,)
+
+    def _decode_program(self, z):
         n, c, h, w = z.shape
         key = (n, h, w, tuple((p.data_ptr(), p._version) for p in self.parameters()))
         prog = self._programs.get((n, h, w))
         if prog is None or prog[0] != key:
             prog = (key, VaeDecodeProgram(self.cfg, self.state_dict(), n, h, w, self.device))
             self._programs[(n, h, w)] = prog
-        out = prog[1].forward(z).to(z.dtype)
-        return _Sample(out) if return_dict else (out,)
+        return prog[1]
+
+    @torch.no_grad()
+    def decode_uint8(self, z):
+        """z (n, 4, h, w) -> device uint8 frames (n, 8h, 8w, 3): the decode plan, then rcdm_frames_to_u8 straight from the
+        decoder's f16 pixel rows — trunc(clamp(x / 2 + 0.5, 0, 1) * 255), what RCDMs_pipeline.py:274-287 and the driver's
+        `(x * 255).astype(uint8)` make of `decode(z).sample`, without the fp32 NCHW tensor in between."""
+        if self.device.type != "cuda":
+            raise hip.RcdmError(f"AutoencoderKLDecoder runs on the HIP path only (module is on {self.device})")
+        return self._decode_program(z).forward_uint8(z)
 
 
 class DiagonalGaussianDistribution:
@@ -185,13 +197,32 @@ class AutoencoderKL(AutoencoderKLDecoder):
         if self.device.type != "cuda":
             raise hip.RcdmError(f"AutoencoderKL runs on the HIP path only (module is on {self.device})")
         n, c, h, w = x.shape
+        mean, logvar = self._encode_program(n, h, w).forward(x)
+        dist = DiagonalGaussianDistribution(mean.to(x.dtype), logvar.to(x.dtype))
+        return _Posterior(dist) if return_dict else (dist,)
+
+    def _encode_program(self, n, h, w):
         key = (n, h, w, tuple((p.data_ptr(), p._version) for p in self.parameters()))
         prog = self._enc_programs.get((n, h, w))
         if prog is None or prog[0] != key:
             prog = (key, VaeEncodeProgram(self.cfg, self.state_dict(), n, h, w, self.device))
             self._enc_programs[(n, h, w)] = prog
-        mean, logvar = prog[1].forward(x)
-        dist = DiagonalGaussianDistribution(mean.to(x.dtype), logvar.to(x.dtype))
+        return prog[1]
+
+    @torch.no_grad()
+    def encode_frames(self, frames, transform, return_dict=True):
+        """`encode(transform(frames))` for uint8 frames and an rcdms_amd.image.FrameTransform, without the fp32 tensor:
+        the transform writes its f16 pixel rows straight into the encode plan's input buffer.  Same posterior, bit for bit."""
+        if self.device.type != "cuda":
+            raise hip.RcdmError(f"AutoencoderKL runs on the HIP path only (module is on {self.device})")
+        from .image import to_device_frames
+        groups = to_device_frames(frames, self.device)
+        if len(groups) != 1:
+            raise ValueError("encode_frames takes one batch of equally sized frames")
+        n = groups[0].shape[0]
+        mean, logvar = self._encode_program(n, transform.height, transform.width).forward_rows(
+            lambda rows: transform(groups[0], rows=True, out=rows), keep=groups[0])
+        dist = DiagonalGaussianDistribution(mean.to(self.dtype), logvar.to(self.dtype))
         return _Posterior(dist) if return_dict else (dist,)
 
 
@@ -297,6 +328,25 @@ class VaeDecodeProgram:
         z32.record_stream(self.stream)
         return out[:, :, 0]
 
+    @torch.no_grad()
+    def forward_uint8(self, z):
+        """As forward, but the f16 pixel rows go straight to uint8 frames (n, H, W, 3)."""
+        from .image import frames_to_uint8
+        n, c, h, w = z.shape
+        assert (n, h, w) == (self.n, self.h, self.w)
+        cur = torch.cuda.current_stream(self.device)
+        z32 = z.detach().to(self.device, torch.float32).contiguous()
+        g = self.out_geo
+        out = torch.empty(n, g.H, g.W, 3, dtype=torch.uint8, device=self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            hip.ncfhw_to_rows(z32.data_ptr(), n, c, 1, h, w, self.z_rows.ptr, self.z_rows.ld, 8)
+            self.plan.run()
+            frames_to_uint8((self.out_rows, n, g.H, g.W), out=out)
+        cur.wait_stream(self.stream)
+        z32.record_stream(self.stream)
+        return out
+
 
 class VaeEncodeProgram:
     """Static launch plan of AutoencoderKL.encode for n images of H x W pixels: -> posterior mean and clamped logvar."""
@@ -365,6 +415,25 @@ class VaeEncodeProgram:
             hip.rows_to_ncfhw(self.out_rows.ptr, self.out_rows.ld, n, 2 * lc, 1, g.H, g.W, out.data_ptr())
         cur.wait_stream(self.stream)
         x32.record_stream(self.stream)
+        mean, logvar = out[:, :lc, 0], out[:, lc:, 0]
+        return mean, logvar.clamp(-30.0, 20.0)
+
+    @torch.no_grad()
+    def forward_rows(self, fill, keep=None):
+        """As forward, with the pixel rows written by `fill(self.x_in)` on the plan's stream (rcdms_amd.image.FrameTransform
+        with rows=True) instead of converted from an fp32 tensor; keep: the device tensor `fill` reads."""
+        n, H, W = self.n, self.H, self.W
+        cur = torch.cuda.current_stream(self.device)
+        g, lc = self.out_geo, self.cfg["latent_channels"]
+        out = torch.empty(n, 2 * lc, 1, g.H, g.W, dtype=torch.float32, device=self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            fill(self.x_in)
+            self.plan.run()
+            hip.rows_to_ncfhw(self.out_rows.ptr, self.out_rows.ld, n, 2 * lc, 1, g.H, g.W, out.data_ptr())
+        cur.wait_stream(self.stream)
+        if keep is not None:
+            keep.record_stream(self.stream)
         mean, logvar = out[:, :lc, 0], out[:, lc:, 0]
         return mean, logvar.clamp(-30.0, 20.0)
 

@@ -194,6 +194,19 @@ class RCDMsPipeline:
         video = video.reshape(-1, f, *video.shape[1:]).permute(0, 2, 1, 3, 4)
         return (video / 2 + 0.5).clamp(0, 1).cpu().float().numpy()
 
+    def decode_latents_uint8(self, latents):
+        """output_type="uint8": the frames of decode_latents truncated to bytes — trunc(clamp(x / 2 + 0.5, 0, 1) * 255), the
+        driver's `(x * 255).astype(uint8)` — as a device uint8 tensor (b, f, H, W, 3).  With the HIP decoder the bytes come
+        straight from its f16 pixel rows (decode_uint8); with any other `vae` from its fp32 sample (frames_to_uint8)."""
+        from rcdms_amd.image import frames_to_uint8
+        f = latents.shape[2]
+        latents = (1 / 0.18215 * latents).permute(0, 2, 1, 3, 4).reshape(-1, latents.shape[1], *latents.shape[3:])
+        if self.vae_decoder is not None:
+            frames = self.vae_decoder.decode_uint8(latents)
+        else:
+            frames = frames_to_uint8(torch.cat([self.vae.decode(latents[i:i + 1]).sample for i in range(latents.shape[0])]))
+        return frames.reshape(-1, f, *frames.shape[1:])
+
     def prepare_extra_step_kwargs(self, generator, eta):
         params = set(inspect.signature(self.scheduler.step).parameters.keys())
         kw = {}
@@ -301,6 +314,9 @@ class RCDMsPipeline:
             if callback is None:
                 bar.update(num_inference_steps)
 
+        if output_type == "uint8":
+            video = self.decode_latents_uint8(final.to(text_embeddings.dtype))
+            return RCDMsPipelineOutput(videos=video) if return_dict else video
         video = self.decode_latents(final.to(text_embeddings.dtype))
         if output_type == "tensor":
             video = torch.from_numpy(video)
