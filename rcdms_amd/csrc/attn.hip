@@ -443,6 +443,12 @@ __global__ __launch_bounds__(NW * 64, (MASKED && DS >= 5) ? 1 : 2) void flash_at
   }
 }
 
+// RCDM_ATTN_XCD=0: blocks in plain (batch, head, query block) order (A/B switch)
+int attn_xcd_mode() {
+  static const int mode = rcdm_env_int("RCDM_ATTN_XCD", 1);
+  return mode;
+}
+
 template <int DS>
 int launch_flash(const AttnArgs& a_in, hipStream_t stream) {
   constexpr int DF = (DS + 1) / 2;
@@ -450,11 +456,7 @@ int launch_flash(const AttnArgs& a_in, hipStream_t stream) {
   const size_t lds = (size_t)2 * (KT * KP + KT * v_row_halfs(DF)) * sizeof(f16);  // ping-pong K and V images
   // (256-query, 8-wave blocks were measured 3-30 % SLOWER on every shape — the K/V stream is not what binds, an 8-wave barrier
   // per key tile costs more — and are not instantiated any more)
-  static int xcd_mode = -1;
-  if (xcd_mode < 0) {
-    const char* e = getenv("RCDM_ATTN_XCD");
-    xcd_mode = e ? atoi(e) : 1;
-  }
+  const int xcd_mode = attn_xcd_mode();
   AttnArgs a = a_in;
   a.plain_order = xcd_mode ? 0 : 1;
   if (a.kvalid || a.causal) {
@@ -462,11 +464,7 @@ int launch_flash(const AttnArgs& a_in, hipStream_t stream) {
     hipLaunchKernelGGL((flash_attn_kernel<DS, 1, (DS <= 5), true, 4>), grid, dim3(256), lds, stream, a);
   } else {
     dim3 grid(((a.Lq + 127) / 128) * a.heads * a.batch);
-    static int msub_mode = -1;  // RCDM_ATTN_MSUB=0: the fma-based softmax everywhere (A/B switch)
-    if (msub_mode < 0) {
-      const char* e = getenv("RCDM_ATTN_MSUB");
-      msub_mode = e ? atoi(e) : 1;
-    }
+    static const int msub_mode = rcdm_env_int("RCDM_ATTN_MSUB", 1);  // RCDM_ATTN_MSUB=0: the fma-based softmax everywhere (A/B switch)
     {
       // d = 40: a spare QK^T column (40 of 48), a V ones-row (row sums in fp32 out of the PV MFMA) and a long key loop
       if constexpr (DS == 3) {
@@ -843,11 +841,7 @@ int rcdm_flash_attn_masked(const rcdm_attn_desc* d, const void* Q, const void* K
   if (wide_head) {
     // (so are its Q and O rows)
     if ((size_t)d->Lq * (size_t)(d->ldq > d->ldo ? d->ldq : d->ldo) * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
-    static int xcd_mode = -1;
-    if (xcd_mode < 0) {
-      const char* e = getenv("RCDM_ATTN_XCD");
-      xcd_mode = e ? atoi(e) : 1;
-    }
+    const int xcd_mode = attn_xcd_mode();
     AttnWideArgs w;
     w.Q = (const f16*)Q; w.K = (const f16*)K; w.V = (const f16*)V; w.O = (f16*)out;
     w.batch = d->batch; w.heads = d->heads; w.Lq = d->Lq; w.Lk = d->Lk; w.d = d->d;
@@ -872,11 +866,7 @@ int rcdm_flash_attn_masked(const rcdm_attn_desc* d, const void* Q, const void* K
   if (ds <= 3) return launch_flash<3>(a, stream);
   if (ds <= 5) return launch_flash<5>(a, stream);
   // 80 < d <= 112 (the 104-wide heads of the CLIP-bigG vision tower): QK^T padded to 112 and PV to 128 instead of 160 / 160
-  static int ds7_mode = -1;  // RCDM_ATTN_DS7=0: the 160-wide form for these heads too (A/B switch)
-  if (ds7_mode < 0) {
-    const char* e = getenv("RCDM_ATTN_DS7");
-    ds7_mode = e ? atoi(e) : 1;
-  }
+  static const int ds7_mode = rcdm_env_int("RCDM_ATTN_DS7", 1);  // RCDM_ATTN_DS7=0: the 160-wide form for these heads too (A/B switch)
   if (ds7_mode && (ds == 6 || ds == 7)) return launch_flash<7>(a, stream);
   return launch_flash<10>(a, stream);
 }
@@ -928,11 +918,7 @@ int rcdm_xattn(const rcdm_attn_desc* d, const void* Q, const void* image, void* 
   a.ldq = d->ldq; a.ldo = d->ldo;
   a.c = d->scale * 1.4426950408889634f;
   const int DF_ = (DS + 1) / 2;
-  static int nw_mode = -1;  // RCDM_XATTN_WAVES=4|8: waves (x 32 queries) per block (A/B switch)
-  if (nw_mode < 0) {
-    const char* e = getenv("RCDM_XATTN_WAVES");
-    nw_mode = e ? atoi(e) : 4;
-  }
+  static const int nw_mode = rcdm_env_int("RCDM_XATTN_WAVES", 4);  // RCDM_XATTN_WAVES=4|8: waves (x 32 queries) per block (A/B switch)
   // Back to back (round 2) 8 waves won at the 64x64 level (21.2 us against 26.7 for 4, 23.5 for 16); in the replayed step
   // graph 4 waves are -0.07 ms per step over the sixteen launches (round 5, five same-box pairs: twice the blocks for the
   // 16x16 / 8x8 levels' 80 heads, and a cold image reaches 4 waves sooner than 8)
@@ -940,19 +926,11 @@ int rcdm_xattn(const rcdm_attn_desc* d, const void* Q, const void* image, void* 
   // query chunks per block: as many (<= 4 with 8 waves, <= 2 with 4) as leave one block per CU (RCDM_XATTN_QI overrides: A/B
   // switch).  Same-box A/B at the 64x64 level's five launches, 8 waves: 1 / 2 / 4 chunks = 17.685 / 17.645 / 17.638 ms per step;
   // with 4 waves the chunk count is within the noise (1 / 2 / 4: 17.28 / 17.27 / 17.28)
-  static int qi_mode = -1;
-  if (qi_mode < 0) {
-    const char* e = getenv("RCDM_XATTN_QI");
-    qi_mode = e ? atoi(e) : 0;
-  }
+  static const int qi_mode = rcdm_env_int("RCDM_XATTN_QI", 0);
   const int nqb = (d->Lq + nw * 32 - 1) / (nw * 32);
   int qi = qi_mode > 0 ? qi_mode : 1;
   if (qi_mode <= 0) {
-    static int cus = 0;
-    if (cus <= 0) {
-      int dev = 0, n = 0;
-      cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
+    const int cus = rcdm_num_cus();
     const int cap = nw == 8 ? 4 : 2;
     while (qi < cap && d->batch * d->heads * ((nqb + 2 * qi - 1) / (2 * qi)) >= cus) qi *= 2;
   }
@@ -989,11 +967,7 @@ int rcdm_temporal_attn(const rcdm_temporal_attn_desc* d, const void* qkv, void* 
   const size_t px_bytes = (size_t)d->frames * 3 * C * sizeof(f16);   // LDS per pixel
   // measured (tools/kbench.py attn --only temporal): 32 KB blocks run the 64x64 / 32x32 levels at 4.1 / 3.5 TB/s, 60 KB
   // blocks (two per CU) at 2.9 / 2.5 — the three phases (stage, compute, store) of a block do not overlap, more blocks do
-  static int lds_cap_kb = -1;  // RCDM_TATTN_KB: LDS per block (A/B switch)
-  if (lds_cap_kb < 0) {
-    const char* e = getenv("RCDM_TATTN_KB");
-    lds_cap_kb = e ? atoi(e) : 32;
-  }
+  static const int lds_cap_kb = rcdm_env_int("RCDM_TATTN_KB", 32);  // RCDM_TATTN_KB: LDS per block (A/B switch)
   int tpb = (int)(((size_t)lds_cap_kb * 1024) / px_bytes);
   const int by_threads = 256 / (d->heads * d->frames);
   if (tpb > by_threads) tpb = by_threads;

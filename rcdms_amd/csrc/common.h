@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/rcdm.h"
 
 typedef _Float16 f16;
@@ -40,6 +41,15 @@ static inline bool rcdm_first_on_device(bool (&done)[64]) {
   done[dev] = true;
   return true;
 }
+
+// An integer environment switch (unset: dflt).  Read once per process: the call site latches the value, either in a
+// `static const int` or in a global that the switch's setter resets to -1 ("back to the environment").
+static inline int rcdm_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// CU count of the current device, 256 (the MI355X's) if there is none; read once per process.  Defined in runtime.hip.
+int rcdm_num_cus();
 
 // v_rcp_f32 (1 ulp) instead of an IEEE division: `a / b` and __frcp_rn expand to ~12 VALU ops on gfx950
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

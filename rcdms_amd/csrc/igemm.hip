@@ -28,7 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
-#include "igemm_args.h"
+#include "igemm_plan.h"
 #include "gn_plan.h"
 #ifndef RCDM_LNX_ABLATE
 #define RCDM_LNX_ABLATE 0   // debug builds (tools/lnx_bench.py): 1 = no partial-statistics loads, 64 = no accumulator transform, 128 = no table write, 256 = no producer statistics
@@ -881,585 +881,130 @@ int launch_splitk_reduce(const IgemmArgs& a, hipStream_t stream) {
   return rcdm_check_launch();
 }
 
-// variant: 1 = 128x128 (2 blocks/CU), 2 = 256x256 (1), 3 = 64x64 two-slot ring (4), 4 = 64x64 four-slot ring (2),
-// 5 = 128x64 (3); 6 / 7 / 8 = the ping-pong kernel of igemm8.hip at 160x320 / 160x256 / 256x256; 9 = the 160x160 kernel of
-// igemm16.hip (2); 10 = 128x64 with a three-slot ring (2; GEMMs)   (-1 = heuristic)
-int g_force_variant = -1;
-// f16 split-K slabs on the 160x160 and the LDS-DMA kernels (IgemmArgs::slab16): -1 = not set (environment RCDM_SLAB16, default below)
-int g_slab16 = -1;
-int slab16_mode() {
-  if (g_slab16 < 0) {
-    const char* e = getenv("RCDM_SLAB16");
-    g_slab16 = e ? (atoi(e) != 0) : 1;   // (five same-box pairs: -0.11 ms per step, whole-UNet error unchanged)
-  }
-  return g_slab16;
-}
-struct TileCfg { int bm, bn, blocks_per_cu; };
-constexpr int kFirstPP = 6;
-constexpr int kVar16 = 9;  // igemm16.hip: 160x160, two blocks per CU
-// 10: the igemm_dma loop at 128x64 with a THREE-slot LDS ring, two blocks per CU (GEMMs only; a conv runs as 5).  Measured
-// in the replayed graph (profiles/r4_shape_rules_ab.txt): -0.09 ms per step on the thirty-five N = C = K = 1280 projections of
-// the 16x16 level, worse everywhere else — as were a four-slot 128x64 ring and a three-slot 128x128 ring (one block per CU
-// each; built, tested, removed): one more stage in flight pays only where it does not cost the third co-resident block
-// more than the latency it hides.
-constexpr int kFirstDeep = 10, kNumVariants = 11;
-const TileCfg kTiles[kNumVariants] = {{128, 128, 2}, {128, 128, 2}, {256, 256, 1}, {64, 64, 4}, {64, 64, 2}, {128, 64, 3},
-                                      {160, 320, 1}, {160, 256, 1}, {256, 256, 1}, {160, 160, 2},
-                                      {128, 64, 2}};
-inline bool is_pp(int v) { return v >= kFirstPP && v < kVar16; }
-inline bool is_dma(int v) { return v < kFirstPP || v >= kFirstDeep; }
-int g_pp_mode = -1;  // RCDM_PP=0: never pick the ping-pong kernel (A/B switch)
-int g_num_cus = 0;
 long long* g_trace = nullptr;
 
-int num_cus() {
-  if (g_num_cus <= 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      g_num_cus = n;
-    else
-      g_num_cus = 256;
+// The split-K slabs of a planned launch: a.partial points into the caller's workspace (null when the launch is not split)
+int bind_slabs(IgemmArgs& a, void* workspace, size_t workspace_bytes) {
+  a.partial = nullptr;
+  if (a.splits > 1) {
+    if (!workspace || workspace_bytes < slab_bytes(a)) return RCDM_EWORKSPACE;
+    a.partial = (float*)workspace;
   }
-  return g_num_cus;
+  return RCDM_OK;
 }
 
-// Split-K for the ping-pong kernel: its tiles are big, so shapes with fewer tiles than CUs (M = 10240 / 2560 rows with
-// N = 640 / 1280) are cut along K until one round of the chip is full; a slice keeps >= 16 k-steps.
-// taps of a launch: 1 (GEMM), 9 (conv3x3), 4 (phase form); the W row holds taps * Cin columns (+ Cin2 of a second input)
-inline int taps_of(const IgemmArgs& a) { return (a.Ktot - a.Cin2) / a.Cin; }
-
-int pp_splits(int tiles, int nk) {
-  int s = num_cus() / (tiles > 0 ? tiles : 1);
-  if (s > nk / 16) s = nk / 16;
-  if (s > 8) s = 8;
-  return s < 1 ? 1 : s;
+// "launch, then reduce if split": the tail behind every kernel family (rc: what the GEMM launch returned)
+int reduce_if_split(int rc, const IgemmArgs& a, hipStream_t stream) {
+  return (rc == RCDM_OK && a.splits > 1) ? launch_splitk_reduce(a, stream) : rc;
 }
 
-// The ping-pong kernel (igemm8.hip).  Measured against the 128x128 / 256x256 one-barrier kernels (tools/kbench.py,
-// profiles/r2_pp_kbench.txt): it wins where its big tile comes out as whole rounds of the chip AND the k-loop is long
-// enough to amortise a prologue / epilogue that nothing overlaps (one block per CU): the conv3x3 of the 64x64 level
-// (160x320: exactly 256 tiles, 1.37-1.42x), the other convs with >= 2560 rows (1.04-1.07x), and the M = 40960 GEMMs
-// with N <= 960 (qkv 1.13x, feed-forward out 1.12x).  The K = 640 / 1280 GEMMs of the 32x32 / 16x16 levels stay on the
-// two-blocks-per-CU kernel, whose second block hides the epilogue.  Returns the shape index or -1.
-int pick_pp(const IgemmArgs& a) {
-  const int taps = taps_of(a);
-  const int nk = (a.Cin + BK - 1) / BK * taps;
-  if (a.M < 2048 || a.N < 256) return -1;
-  if (taps == 1) {
-    if (a.M < 20480 || a.N > 1024) return -1;
-    // (nk 10 / 15: the 1x1 shortcut convs of the 64x64 level, tools/autotune.py + same-box A/B in the graph)
-    if (!(nk >= 10 || (a.N >= 640 && nk >= 5))) return -1;
-  } else if (nk < 40) {
-    return -1;
-  }
-  const int cus = num_cus();
-  int best = -1;
-  float best_score = 0.80f;
-  for (int sh = 0; sh < kNumPPShapes; ++sh) {
-    const int bm = kPPShapes[sh].bm, bn = kPPShapes[sh].bn;
-    const int tm = (a.M + bm - 1) / bm, tn = (a.N + bn - 1) / bn, tiles = tm * tn;
-    const int sp = tiles < cus ? pp_splits(tiles, nk) : 1;
-    const int work = tiles * sp, rounds = (work + cus - 1) / cus;
-    const float useful = (float)a.M * (float)a.N / ((float)tiles * bm * bn);
-    const float fill = (float)work / (float)(rounds * cus);
-    float score = useful * fill * (sp > 1 ? 0.90f : 1.0f);
-    if (sh == 2) score *= 1.03f;  // 256x256 moves fewer operand bytes per flop
-    if (score > best_score) {
-      best_score = score;
-      best = sh;
-    }
-  }
-  return best;
-}
-
-// The 160x160 two-blocks-per-CU kernel (igemm16.hip), measured against every other variant (tools/kbench.py,
-// profiles/r2_kbench.txt): it wins on the wide-N GEMMs with K <= 1280 and >= 2560 rows — fused [q;k;v] and GEGLU
-// projections of the 64x64 / 32x32 / 16x16 levels: 7-15 % (no padded columns at N = 960 / 1920, 20 % fewer operand bytes
-// per flop than 128x128, and unlike the ping-pong kernel its epilogue hides under the CU's other block) — and on the convs
-// of the 32x32 level (3 % over the ping-pong kernel, which needs split-K there).  N = C GEMMs (HBM-bound or too few
-// tiles), K >= 2560 (split-K shapes) and the 8x8 level stay where they were.
-bool pick_16(const IgemmArgs& a) {
-  static int mode = -1;  // RCDM_I16=0: never (A/B switch)
-  if (mode < 0) {
-    const char* e = getenv("RCDM_I16");
-    mode = e ? atoi(e) : 1;
-  }
-  if (!mode) return false;
-  const int taps = taps_of(a);
-  if (taps == 1) {
-    // plain projections (no epilogue work: the staged halfs are copied out) that split into whole rounds of 160x160 tiles:
-    // the cross-attention queries of the 32x32 level and of the shared-prefix half batch (tools/autotune.py: 17.3 -> 13.8 us)
-    const bool plain = a.epi == 0 || (a.lnx_stat && !(a.epi & (RCDM_EPI_RESIDUAL | RCDM_EPI_GELU | RCDM_EPI_GEGLU)));
-    if (plain && a.out_scale == 1.0f && a.M % 160 == 0 && a.N % 160 == 0 && (a.M / 160) * (a.N / 160) >= 256 &&
-        a.Cin <= 640 && a.N <= 640)
-      return true;
-    return a.N >= 960 && a.N >= 3 * a.Cin && a.M >= 2048 && a.Cin <= 1280;  // wide N only: qkv (3C), GEGLU (8C)
-  }
-  return a.M >= 5120 && a.M < 20480 && a.N >= 640 && a.N <= 1280;
-}
-
-// Per-shape overrides of the heuristics below: {taps, M, N, C_in} -> tile variant (1 .. 10) and split-K factor (0 = that
-// variant's own heuristic).  kShapeRules holds what tools/autotune.py found AND a same-box A/B of the whole step
-// confirmed; RCDM_SHAPE_RULES="taps,M,N,Cin,variant,split;..." adds rules at run time (first match wins: the environment's
-// rules are looked at first), RCDM_SHAPE_RULES=off ignores the table — for tuning another chip or another model without
-// a rebuild.  A rule is skipped where its variant cannot run the launch (row statistics: variants 1 .. 5; deferred-
-// LayerNorm consumers: not the ping-pong kernel).
-struct ShapeRule { int taps, M, N, Cin, variant, split; };
-const ShapeRule kShapeRules[] = {
-    // the headline workload (b = 2 x 5 frames, 64x64 latents), round 4: profiles/r4_autotune.txt, profiles/r4_shape_rules_ab.txt
-    {9, 40960, 320, 320, kVar16, 1},   // the convs of the 64x64 level on 160x160 tiles, two blocks per CU, instead of the
-    {9, 40960, 320, 640, kVar16, 1},   //   160x320 ping-pong tile (-3 % back to back, -0.15 ms per step together in the graph)
-    {9, 40960, 320, 960, kVar16, 1},
-    {9, 20480, 320, 320, kVar16, 0},   // ... and of the shared-prefix half batch
-    {1, 2560, 1280, 1280, 10, 0},      // the N = C projections of the 16x16 level (to_out, proj_in, to_q) on the three-slot 128x64 ring: -0.09 ms
-    {1, 640, 1280, 2560, 3, 3},        // 1x1 shortcuts of the 8x8 up blocks: 64x64 tiles split 3 ways
-    // tools/tune_rules.py (every shape timed inside the step's launch sequence), then tools/ab_rules.sh: -0.07 ms together
-    {1, 2560, 1280, 6400, kVar16, 0},  // proj_out-composed feed-forward GEMMs (K = 5C): 16x16 level on 160x160 tiles,
-    {1, 10240, 640, 3200, 1, 0},       //   32x32 level on 128x128, 8x8 level on the three-slot 128x64 ring
-    {1, 640, 1280, 6400, 10, 0},
-    {1, 2560, 1280, 2560, 10, 0},      // 1x1 shortcuts / downsample-level projections of the 16x16 level: three-slot 128x64 ring
-    {1, 2560, 1280, 1920, 10, 0},
-    {1, 2560, 1280, 640, 10, 0},
-    {1, 40960, 320, 640, kVar16, 0},   // 1x1 shortcuts of the 64x64 up blocks on 160x160 tiles
-    {1, 40960, 320, 960, kVar16, 0},
-    // the shapes only BASELINE config 1's plan has (b = 2 x 5 frames, 32x32 latents): tools/tune_rules.py --latent 32, confirmed
-    // together in the graph (183.1 -> 173.9 ms per 20-step story; profiles/r4_shape_rules_ab.txt)
-    {1, 2560, 640, 3200, 4, 0}, {1, 10240, 320, 1600, 10, 0}, {1, 2560, 640, 640, 4, 0}, {9, 160, 1280, 1280, 5, 0},
-    {1, 160, 1280, 6400, 10, 0}, {1, 160, 10240, 1280, 4, 0}, {9, 10240, 320, 640, kVar16, 0},
-    {1, 160, 1280, 2560, 10, 4}, {9, 10240, 320, 960, kVar16, 4}, {9, 2560, 640, 1920, kVar16, 0},
-    {1, 10240, 320, 320, 10, 0}, {9, 2560, 640, 1280, kVar16, 0}, {9, 2560, 640, 960, kVar16, 8},
-    {9, 5120, 320, 320, 1, 4}, {9, 640, 1280, 640, 1, 8}, {9, 2560, 640, 320, 1, 4}, {9, 640, 640, 640, 1, 8},
-    {9, 2560, 320, 320, kVar16, 8}, {1, 2560, 640, 1920, 4, 0}, {1, 640, 1280, 1920, 10, 4},
-    {9, 10240, 8, 320, kVar16, 8}, {1, 10240, 320, 960, 10, 0}, {1, 2560, 640, 1280, 4, 0}, {9, 5120, 320, 64, 5, 0},
-    {1, 2560, 640, 960, 4, 0}, {1, 5120, 320, 320, 4, 0}, {1, 640, 1280, 640, 4, 0}, {1, 2560, 640, 320, 4, 0},
-    // the shapes only BASELINE config 3's plan has (4 stories = b 8, 64x64 latents, L = 91): --stories 4 --ctx-len 91, confirmed
-    // together (2741 -> 2683 ms per story batch): at this batch the 160x160 two-blocks-per-CU kernel beats the ping-pong tiles on
-    // every conv of the 64x64 / 32x32 levels in the step's own sequence, not back to back
-    {1, 40960, 5120, 640, 2, 0}, {1, 10240, 1280, 6400, kVar16, 1}, {9, 40960, 640, 640, kVar16, 0},
-    {9, 163840, 320, 640, kVar16, 1}, {9, 163840, 320, 960, kVar16, 0}, {9, 40960, 640, 1920, kVar16, 1},
-    {9, 40960, 640, 1280, kVar16, 1}, {9, 40960, 640, 960, kVar16, 0}, {1, 10240, 1280, 1280, kVar16, 1},
-    {9, 40960, 640, 320, kVar16, 1}, {1, 10240, 1280, 2560, kVar16, 1}, {1, 40960, 640, 1920, kVar16, 0},
-    {1, 40960, 640, 1280, kVar16, 1}, {9, 81920, 320, 64, kVar16, 1}, {1, 10240, 1280, 1920, kVar16, 0},
-    {1, 40960, 640, 320, 5, 1}, {1, 81920, 320, 320, 5, 1}, {1, 10240, 1280, 640, kVar16, 0},
-    // BASELINE config 5 (stage-1 prior, 970 token rows): tools/tune_rules.py --prior, confirmed with tools/bench_prior.py (1.83 -> 1.92 stories/s)
-    {1, 970, 2048, 2048, 4, 0}, {1, 970, 6144, 2048, 5, 1}, {1, 10, 1280, 2048, 10, 4},
-    {0, 0, 0, 0, 0, 0},   // (terminator)
+// The igemm_dma_kernel instantiations: (tile of the LDS-DMA family, what the launch's epilogue does) -> kernel, nullptr where
+// kVariants says the tile cannot run it.  Every kernel pointer comes from here — for the one-time dynamic-LDS attribute pass
+// and for the launch alike — so an instantiation cannot be launched without having had its attribute set (a missing one
+// would fail only on the first launch that needs more than 64 KB on a fresh device).
+enum DmaMode {
+  kDmaFused,      // direct launch with the fused epilogue (E16 = true: f16 staging)
+  kDmaSlab,       // split-K slab writer (E16 = false: fp32 staging)
+  kDmaStats,      // GEMMs, LX = 1: fused epilogue + row statistics (deferred-LayerNorm producer)
+  kDmaConsumer,   // GEMMs, LX = 2: deferred-LayerNorm consumer (+ statistics)
+  kDmaQuickGelu,  // GEMMs, LX = 4: the quick-GELU epilogue
+  kNumDmaModes
 };
-constexpr int kMaxEnvRules = 128;
-ShapeRule g_env_rules[kMaxEnvRules];
-int g_n_env = -1;            // -1: RCDM_SHAPE_RULES not parsed yet
-bool g_rule_table_on = true;
-char g_rules_text[8192] = "";
-bool g_rules_from_api = false;
-const ShapeRule* find_shape_rule(const IgemmArgs& a) {
-  ShapeRule* env_rules = g_env_rules;
-  int& n_env = g_n_env;
-  bool& table_on = g_rule_table_on;
-  if (n_env < 0) {
-    int n = 0;
-    const char* e = g_rules_from_api ? g_rules_text : getenv("RCDM_SHAPE_RULES");
-    table_on = true;
-    if (e && !strcmp(e, "off")) {
-      table_on = false;
-    } else if (e) {
-      while (*e && n < kMaxEnvRules) {
-        ShapeRule r{};
-        int used = 0;
-        if (sscanf(e, "%d,%d,%d,%d,%d,%d%n", &r.taps, &r.M, &r.N, &r.Cin, &r.variant, &r.split, &used) == 6 && r.variant >= 1 &&
-            r.variant < kNumVariants && r.split >= 0)
-          env_rules[n++] = r;
-        e += used;
-        while (*e && *e != ';') ++e;
-        if (*e == ';') ++e;
-        if (!used) break;
-      }
-    }
-    n_env = n;
+using DmaKernel = void (*)(const IgemmArgs);
+
+template <int TAPS, int V>
+DmaKernel dma_kernel_of(DmaMode mode) {
+  constexpr VariantRow r = kVariants[V];
+  static_assert(r.family == kFamDma, "not an igemm_dma_kernel tile");
+  if constexpr (TAPS == 1 || !(r.cannot & kNoConv)) {
+    if (mode == kDmaFused) return igemm_dma_kernel<TAPS, r.bm, r.bn, r.wm, r.wn, r.ring, true>;
+    if (mode == kDmaSlab) return igemm_dma_kernel<TAPS, r.bm, r.bn, r.wm, r.wn, r.ring, false>;
   }
-  if (a.ph_rows) return nullptr;
-  const int taps = taps_of(a);
-  auto fits = [&](const ShapeRule& r) {
-    if (r.taps != taps || r.M != a.M || r.N != a.N || r.Cin != a.Cin) return false;
-    if (a.stat_out && !is_dma(r.variant)) return false;
-    if (a.lnx_stat && is_pp(r.variant)) return false;
-    if ((a.stat_out || a.lnx_stat) && r.split > 1) return false;
-    return true;
-  };
-  for (int i = 0; i < n_env; ++i)
-    if (fits(env_rules[i])) return &env_rules[i];
-  if (table_on)
-    for (const ShapeRule* r = kShapeRules; r->variant; ++r)
-      if (fits(*r)) return r;
+  if constexpr (TAPS == 1 && !(r.cannot & kNoStats))
+    if (mode == kDmaStats) return igemm_dma_kernel<TAPS, r.bm, r.bn, r.wm, r.wn, r.ring, true, 1>;
+  if constexpr (TAPS == 1 && !(r.cannot & kNoConsumer))
+    if (mode == kDmaConsumer) return igemm_dma_kernel<TAPS, r.bm, r.bn, r.wm, r.wn, r.ring, true, 2>;
+  if constexpr (TAPS == 1 && !(r.cannot & kNoQuickGelu))
+    if (mode == kDmaQuickGelu) return igemm_dma_kernel<TAPS, r.bm, r.bn, r.wm, r.wn, r.ring, true, 4>;
   return nullptr;
 }
 
-int pick_variant(const IgemmArgs& a) {
-  if (g_force_variant < 0) {
-    const char* e = getenv("RCDM_IGEMM");
-    g_force_variant = 99;
-    if (e && !strcmp(e, "dma128")) g_force_variant = 1;
-    if (e && !strcmp(e, "dma256")) g_force_variant = 2;
-    if (e && !strcmp(e, "dma64")) g_force_variant = 3;
+template <int TAPS>
+DmaKernel dma_kernel(int variant, DmaMode mode) {
+  switch (variant) {
+    case 0:
+    case kVar128: return dma_kernel_of<TAPS, kVar128>(mode);
+    case kVar256: return dma_kernel_of<TAPS, kVar256>(mode);
+    case kVar64: return dma_kernel_of<TAPS, kVar64>(mode);
+    case kVar64Deep: return dma_kernel_of<TAPS, kVar64Deep>(mode);
+    case kVar128x64: return dma_kernel_of<TAPS, kVar128x64>(mode);
+    case kVar128x64Deep: return dma_kernel_of<TAPS, kVar128x64Deep>(mode);
+    default: return nullptr;   // (the other kernel families)
   }
-  if (g_force_variant != 99) return g_force_variant == 0 ? 1 : g_force_variant;
-  if (const ShapeRule* r = find_shape_rule(a)) return r->variant;
-  if (g_pp_mode < 0) {
-    const char* e = getenv("RCDM_PP");
-    g_pp_mode = e ? atoi(e) : 1;
-  }
-  if (g_pp_mode && !a.stat_out) {   // row statistics come out of the igemm_dma epilogue only
-    if (pick_16(a)) return kVar16;
-    const int pp = pick_pp(a);
-    if (pp >= 0) return kFirstPP + pp;
-  }
-  // measured (tools/kbench.py, MI355X).  128x128 with two blocks per CU is the default.  Shapes that leave most CUs
-  // without a 128x128 tile (8x8 / 16x16 levels, context K/V projections) run as 64x64 or 128x64 tiles so that several
-  // blocks per CU keep more DMA in flight; N = 320 / 960 (half a 128-wide tile wasted) with a short K take 128x64;
-  // the deep-K convs of the 32x32 / 16x16 levels take 256x256.
-  const int nk = (a.Cin + BK - 1) / BK * taps_of(a) + (a.Cin2 + BK - 1) / BK;
-  if (a.Ktot != a.Cin) {
-    if (a.N <= 64) return 5;  // conv_out (4 -> 8 channels): half the weight tile of 128x128 is padding (51 -> 28 us)
-    return 1;   // (the 256x256 LDS-DMA tile's conv instantiation spills 48 B: only when forced; the ping-pong 256x256 tile covers its shapes)
-  }
-  const int t128 = ((a.M + 127) / 128) * ((a.N + 127) / 128);
-  if (t128 <= 64 && nk <= 24) return 4;  // (the two-slot 64x64 ring is 8-10 % faster back to back, tools/autotune.py, but +0.1 ms per step in the graph)
-  if (nk >= 20 && nk < 40 && a.N >= 512 && a.M >= 512) {
-    // 256x256 (staggered 8-wave loop, ~8 % faster per flop) when its last round of tiles is not emptier than 128x128's
-    const int cus = num_cus();
-    const int t256 = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-    const float e1 = (float)t128 / (float)(((t128 + 2 * cus - 1) / (2 * cus)) * 2 * cus);
-    const float e2 = (float)t256 / (float)(((t256 + cus - 1) / cus) * cus);
-    if (1.08f * e2 > e1 + 0.01f) return 2;
-  }
-  if (nk >= 40) return 1;  // deep K: split-K over 128x128 tiles fills the chip
-  if (t128 <= 160) return 3;
-  if (t128 <= 256) return 5;
-  if ((a.N % 128) == 64 && nk <= 10) return 5;
-  return 1;
-}
-
-// Split-K only pays when (a) all tiles x splits still run as ONE round of resident blocks (a second, partly filled
-// round costs more than the idle CUs it fills) and (b) every slice keeps >= ~20 k-steps, because the fp32 slabs and
-// the reduce pass are not free (measured with tools/splitk_test.py: e.g. M=2560 N=1280 K=1280 is 21 us unsplit and
-// 33 us split 3 ways; the 8x8-level convs (50 tiles, 180 k-steps) drop from 150 us to 40 us split 8 ways).
-int plan_splits(int tiles, int slots, int nk, int requested) {
-  if (requested == 1) return 1;
-  if (requested > 1) return requested < nk ? requested : nk;
-  int s = slots / (tiles > 0 ? tiles : 1);
-  if (s > nk / 20) s = nk / 20;
-  if (s > 16) s = 16;
-  if (s < 1) s = 1;
-  return s;
-}
-
-int fill_common(IgemmArgs& a, int requested_split, int* variant_out = nullptr, int forced_variant = -1) {
-  int variant = forced_variant >= 0 ? forced_variant : pick_variant(a);
-  // the 256x256 LDS-DMA tile is at the 256-register cap: its statistics / deferred-LayerNorm instantiations spilled (12 /
-  // 200 B of scratch) and are not built — such launches take the 128x128 tile, also when variant 2 is forced
-  // (so did its quick-GELU instantiation, 8 B: the same rule)
-  if (variant == 2 && (a.stat_out || a.lnx_stat || (a.epi & RCDM_EPI_QUICK_GELU))) variant = 1;
-  if (variant_out) *variant_out = variant;
-  const TileCfg& tc = kTiles[variant];
-  a.tilesM = (a.M + tc.bm - 1) / tc.bm;
-  a.tilesN = (a.N + tc.bn - 1) / tc.bn;
-  a.kc = (a.Cin + BK - 1) / BK;
-  const int taps = taps_of(a);
-  a.nk = taps * a.kc;
-  a.nk1 = kNoSeg2;
-  if (a.Cin2 > 0) {          // second input: its k-steps follow the nine taps' (from_conv: Cin and Cin2 are multiples of BK)
-    a.nk1 = a.nk;
-    a.nk += a.Cin2 / BK;
-  }
-  int s;
-  const ShapeRule* rule = (g_force_variant == 99 && requested_split <= 0 && forced_variant < 0) ? find_shape_rule(a) : nullptr;
-  if (rule && rule->split > 0) {
-    s = rule->split;
-  } else if (is_pp(variant) && requested_split <= 0) {
-    const int tiles = a.tilesM * a.tilesN;
-    s = tiles < num_cus() ? pp_splits(tiles, a.nk) : 1;
-  } else {
-    s = plan_splits(a.tilesM * a.tilesN, num_cus() * tc.blocks_per_cu, a.nk, requested_split);
-  }
-  if (s > a.nk) s = a.nk;
-  a.nk_per_split = (a.nk + s - 1) / s;
-  a.splits = (a.nk + a.nk_per_split - 1) / a.nk_per_split;
-  return RCDM_OK;
-}
-
-// A statistics producer whose caller asks for another slot count than this shape's own tile choice gives (two producers
-// that fill ONE statistics buffer — e.g. the same projection run on all rows and on a row subset — must agree on it): the
-// LDS-DMA tile whose column-tile count is `parts` (64- or 128-wide tiles), -1 when there is none.
-int variant_for_parts(const IgemmArgs& a, int parts) {
-  const int n64 = (a.N + 63) / 64, n128 = (a.N + 127) / 128;
-  if (parts == n128) return 1;
-  if (parts == n64) return ((a.M + 127) / 128) * n64 < num_cus() ? 4 : 5;
-  return -1;
-}
-
-int check_common(const IgemmArgs& a) {
-  if (!a.A || !a.W || !a.out) return RCDM_EINVAL;
-  if (a.M <= 0 || a.N <= 0 || a.Cin <= 0) return RCDM_EINVAL;
-  if ((a.Cin & 7) || (a.N & 7) || (a.lda & 7) || (a.ldc & 7)) return RCDM_ESHAPE;
-  if ((a.epi & RCDM_EPI_BIAS) && !a.bias) return RCDM_EINVAL;
-  if ((a.epi & RCDM_EPI_ROWVEC) && (!a.rowvec || a.rows_per_sample <= 0 || (a.ldt & 3))) return RCDM_EINVAL;
-  if ((a.epi & RCDM_EPI_RESIDUAL) && (!a.res || (a.ldr & 7))) return RCDM_EINVAL;
-  if ((a.epi & RCDM_EPI_GEGLU) && (a.N % 32)) return RCDM_ESHAPE;
-  if ((a.epi & RCDM_EPI_GEGLU) && (a.epi & RCDM_EPI_GELU)) return RCDM_EINVAL;
-  if ((a.epi & RCDM_EPI_QUICK_GELU) && (a.epi & (RCDM_EPI_GELU | RCDM_EPI_GEGLU))) return RCDM_EINVAL;
-  if (a.dup < 0) return RCDM_EINVAL;
-  // buffer-load offsets are 32-bit with 0x80000000 reserved as "out of range"
-  const size_t in_rows = (a.Ktot == a.Cin) ? (size_t)a.M : (size_t)(a.M / (a.Ho * a.Wo)) * a.Hi * a.Wi;
-  if (in_rows * (size_t)a.lda * 2 >= 0x7FFFFFFFull || (size_t)a.N * a.Ktot * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
-  return RCDM_OK;
-}
-
-template <typename K>
-void set_lds(K kernel, int bytes) {
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 template <int TAPS>
-int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  constexpr int LTAB = 3072;                       // behind the ring, deferred LayerNorm: [BM][2] floats (rstd, mean rstd) + [BN] floats S
-  constexpr int LDS_128 = 2 * (128 + 128) * 128 + LTAB;   // 64 KB  (two blocks per CU)
-  constexpr int LDS_256 = 2 * (256 + 256) * 128 + LTAB;   // 128 KB
-  constexpr int LDS_64 = 2 * (64 + 64) * 128 + LTAB;      // 32 KB  (four blocks per CU)
-  constexpr int LDS_64D = 4 * (64 + 64) * 128 + LTAB;     // 64 KB  (three steps in flight)
-  constexpr int LDS_128x64 = 2 * (128 + 64) * 128 + LTAB; // 48 KB  (three blocks per CU)
-  constexpr int LDS_128x64_3 = 3 * (128 + 64) * 128 + LTAB;   // 72 KB (two)
-  static bool attr_set[64] = {};
-  if (rcdm_first_on_device(attr_set)) {
-    set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, false>, LDS_128);
-    set_lds(igemm_dma_kernel<TAPS, 256, 256, 2, 4, 2, false>, LDS_256);
-    set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, false>, LDS_64);
-    set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, false>, LDS_64D);
-    set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, false>, LDS_128x64);
-    set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true>, LDS_128);
-    set_lds(igemm_dma_kernel<TAPS, 256, 256, 2, 4, 2, true>, LDS_256);
-    set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true>, LDS_64);
-    set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true>, LDS_64D);
-    set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true>, LDS_128x64);
-    if constexpr (TAPS == 1) {
-#define RCDM_DEEP_LDS(BM, BN, NS, LDS)                                                      \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, false>, LDS);                        \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true>, LDS);                         \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 1>, LDS);                      \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 2>, LDS);                      \
-      set_lds(igemm_dma_kernel<TAPS, BM, BN, 2, 2, NS, true, 4>, LDS)
-      RCDM_DEEP_LDS(128, 64, 3, LDS_128x64_3);
-#undef RCDM_DEEP_LDS
-      set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true, 1>, LDS_128);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true, 1>, LDS_64);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true, 1>, LDS_64D);
-      set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true, 1>, LDS_128x64);
-      set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true, 2>, LDS_128);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true, 2>, LDS_64);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true, 2>, LDS_64D);
-      set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true, 2>, LDS_128x64);
-      set_lds(igemm_dma_kernel<TAPS, 128, 128, 2, 2, 2, true, 4>, LDS_128);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 2, true, 4>, LDS_64);
-      set_lds(igemm_dma_kernel<TAPS, 64, 64, 2, 2, 4, true, 4>, LDS_64D);
-      set_lds(igemm_dma_kernel<TAPS, 128, 64, 2, 2, 2, true, 4>, LDS_128x64);
-    }
-  }
-  if (a.splits > 1) {
-    const size_t need = (size_t)a.splits * a.M * a.N * sizeof(float);
-    if (!workspace || workspace_bytes < need) return RCDM_EWORKSPACE;
-    a.partial = (float*)workspace;
-  } else {
-    a.partial = nullptr;
-  }
-  a.trace = g_trace;
-  a.dbg = 0;
-  if (a.stat_out && (!is_dma(variant) || a.splits > 1 || (a.epi & RCDM_EPI_GEGLU) || a.stat_parts != a.tilesN))
-    return RCDM_ESHAPE;
-  if ((a.stat_out || a.lnx_stat) && TAPS != 1) return RCDM_ESHAPE;
-  if (a.lnx_stat && (a.splits > 1 || !a.lnx_S || a.lnx_parts < 1 || a.lnx_parts > kLnxMaxParts)) return RCDM_ESHAPE;
-  if (a.lnx_stat && variant == kFirstPP + 2) return RCDM_ESHAPE;   // the 256x256 ping-pong tile has no consumer epilogue (register cap); only reachable when that variant is forced
-  if (variant == kVar16) {
-    a.slab16 = a.splits > 1 && slab16_mode() && !(a.epi & RCDM_EPI_GEGLU);
-    int rc = rcdm_igemm16_launch(a, TAPS, stream);
-    if (rc) return rc;
-    if (a.splits > 1) {
-      rc = launch_splitk_reduce(a, stream);
-    }
-    return rc;
-  }
-  if (is_pp(variant)) {
-    static int rotate = -1;
-    if (rotate < 0) {
-      const char* e = getenv("RCDM_PP_ROTATE");
-      rotate = e ? atoi(e) : 0;   // measured: no gain (the weight stream is not hot-spotting L2 channels)
-    }
-    a.dbg = rotate ? 8 : 0;
-    int rc = rcdm_igemm_pp_launch(a, TAPS, variant - kFirstPP, stream);
-    if (rc) return rc;
-    if (a.splits > 1) {
-      rc = launch_splitk_reduce(a, stream);
-    }
-    return rc;
-  }
+int launch_dma(IgemmArgs& a, int variant, hipStream_t stream) {
+  const VariantRow& row = kVariants[variant];
   a.slab16 = a.splits > 1 && slab16_mode() && !(a.epi & RCDM_EPI_GEGLU);
   const int ntiles = a.tilesM * a.tilesN;
-  int gx = num_cus() * kTiles[variant].blocks_per_cu;
+  int gx = rcdm_num_cus() * row.blocks_per_cu;
   if (a.splits > 1) gx = (gx + a.splits - 1) / a.splits;
   gx = (gx + 7) / 8 * 8;  // keep the b%8 -> XCD pattern aligned across the persistent stride
-  static int persist_mode = -1;  // RCDM_PERSIST=0: one tile per block (A/B switch); default: persistent blocks
-  if (persist_mode < 0) {
-    const char* e = getenv("RCDM_PERSIST");
-    persist_mode = e ? atoi(e) : 1;
-  }
+  static const int persist_mode = rcdm_env_int("RCDM_PERSIST", 1);  // RCDM_PERSIST=0: one tile per block (A/B switch); default: persistent blocks
   // (GEGLU launches used to run one tile per block: a persistent block had to drain its epilogue stores before it
   // could trust the next tile's DMA.  With the loads waited for BEFORE the stores that stall is gone.)
   if (persist_mode == 0) gx = ntiles;
   if (gx > ntiles) gx = ntiles;
   dim3 grid(gx, a.splits);
-  // E16 = true: direct launch with the fused epilogue (f16 staging); false: split-K slab writer (fp32 staging)
-  const bool e16 = a.splits == 1;
-  const bool lx = a.stat_out || a.lnx_stat;   // (TAPS == 1 and e16 only: checked above)
-#define RCDM_IGEMM_LAUNCH(BM, BN, WM, WN, NS, THREADS, LDS)                                                           \
-  do {                                                                                                                \
-    if constexpr (TAPS == 1) {                                                                                        \
-      if (a.lnx_stat) {                                                                                               \
-        hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true, 2>), grid, dim3(THREADS), LDS, stream, a); \
-        break;                                                                                                        \
-      }                                                                                                               \
-      if (lx) {                                                                                                       \
-        hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true, 1>), grid, dim3(THREADS), LDS, stream, a); \
-        break;                                                                                                        \
-      }                                                                                                               \
-      if (e16 && (a.epi & RCDM_EPI_QUICK_GELU)) {                                                                     \
-        hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true, 4>), grid, dim3(THREADS), LDS, stream, a); \
-        break;                                                                                                        \
-      }                                                                                                               \
-    }                                                                                                                 \
-    if (e16) hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, true>), grid, dim3(THREADS), LDS, stream, a); \
-    else hipLaunchKernelGGL((igemm_dma_kernel<TAPS, BM, BN, WM, WN, NS, false>), grid, dim3(THREADS), LDS, stream, a);    \
-  } while (0)
-  if (TAPS != 1 && variant >= kFirstDeep) variant = 5;
-  switch (variant) {
-    case 10: if constexpr (TAPS == 1) { RCDM_IGEMM_LAUNCH(128, 64, 2, 2, 3, 256, LDS_128x64_3); } break;
-    case 2:   // (no statistics / consumer instantiations of this tile: fill_common)
-      if (e16) hipLaunchKernelGGL((igemm_dma_kernel<TAPS, 256, 256, 2, 4, 2, true>), grid, dim3(512), LDS_256, stream, a);
-      else hipLaunchKernelGGL((igemm_dma_kernel<TAPS, 256, 256, 2, 4, 2, false>), grid, dim3(512), LDS_256, stream, a);
-      break;
-    case 3: RCDM_IGEMM_LAUNCH(64, 64, 2, 2, 2, 256, LDS_64); break;
-    case 4: RCDM_IGEMM_LAUNCH(64, 64, 2, 2, 4, 256, LDS_64D); break;
-    case 5: RCDM_IGEMM_LAUNCH(128, 64, 2, 2, 2, 256, LDS_128x64); break;
-    default: RCDM_IGEMM_LAUNCH(128, 128, 2, 2, 2, 256, LDS_128);
-  }
-#undef RCDM_IGEMM_LAUNCH
-  int rc = rcdm_check_launch();
+  // (statistics / consumer launches: TAPS == 1 and unsplit only, checked by launch<>)
+  const DmaMode mode = a.lnx_stat ? kDmaConsumer : a.stat_out ? kDmaStats : a.splits > 1 ? kDmaSlab
+                       : (TAPS == 1 && (a.epi & RCDM_EPI_QUICK_GELU)) ? kDmaQuickGelu : kDmaFused;
+  // a conv on the three-slot 128x64 ring runs the two-slot kernel (in the grid planned for the variant asked for)
+  const int kv = (TAPS != 1 && (row.cannot & kNoConv)) ? row.instead : variant;
+  const DmaKernel kernel = dma_kernel<TAPS>(kv, mode);
+  if (!kernel) return RCDM_ESHAPE;   // (fill_common plans no such launch)
+  hipLaunchKernelGGL(kernel, grid, dim3(kVariants[kv].threads()), kVariants[kv].lds_bytes(), stream, a);
+  return rcdm_check_launch();
+}
+
+template <int TAPS>
+int launch(IgemmArgs& a, int variant, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const VariantRow& row = kVariants[variant];
+  static bool attr_set[64] = {};
+  if (rcdm_first_on_device(attr_set))
+    for (int v = 1; v < kNumVariants; ++v)
+      for (int m = 0; m < kNumDmaModes; ++m)
+        if (const DmaKernel k = dma_kernel<TAPS>(v, (DmaMode)m))
+          (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, kVariants[v].lds_bytes());
+  int rc = bind_slabs(a, workspace, workspace_bytes);
   if (rc) return rc;
-  if (a.splits > 1) {
-    rc = launch_splitk_reduce(a, stream);
+  a.trace = g_trace;
+  a.dbg = 0;
+  if (a.stat_out && (row.family != kFamDma || a.splits > 1 || (a.epi & RCDM_EPI_GEGLU) || a.stat_parts != a.tilesN))
+    return RCDM_ESHAPE;
+  if ((a.stat_out || a.lnx_stat) && TAPS != 1) return RCDM_ESHAPE;
+  if (a.lnx_stat && (a.splits > 1 || !a.lnx_S || a.lnx_parts < 1 || a.lnx_parts > kLnxMaxParts)) return RCDM_ESHAPE;
+  if (a.lnx_stat && (row.cannot & kNoConsumer)) return RCDM_ESHAPE;   // the 256x256 ping-pong tile has no consumer epilogue (register cap); only reachable when that variant is forced
+  if (row.family == kFam160) {
+    a.slab16 = a.splits > 1 && slab16_mode() && !(a.epi & RCDM_EPI_GEGLU);
+    rc = rcdm_igemm16_launch(a, TAPS, stream);
+  } else if (row.family == kFamPP) {
+    static const int rotate = rcdm_env_int("RCDM_PP_ROTATE", 0);   // measured: no gain (the weight stream is not hot-spotting L2 channels)
+    a.dbg = rotate ? 8 : 0;
+    rc = rcdm_igemm_pp_launch(a, TAPS, variant - kVarPP, stream);
+  } else {
+    rc = launch_dma<TAPS>(a, variant, stream);
   }
-  return rc;
+  return reduce_if_split(rc, a, stream);
 }
 
-// statistics geometry of the norm behind a split-K launch (rcdm_*_gnstat): 0 when the pair qualifies — `a` planned (splits
-// known), the norm reads exactly the rows this launch writes (same row count, width, row stride), takes the three-launch
-// form, and the epilogue has no GEGLU / second row copy / phase rows.  With gn_ws: also points a.gn_partial into it.
-int attach_gnstat(IgemmArgs& a, const rcdm_groupnorm_desc* gn, void* gn_ws, size_t gn_ws_bytes, bool need_ws) {
-  if (!gn) return RCDM_EINVAL;
-  if (a.epi & RCDM_EPI_QUICK_GELU) return RCDM_ESHAPE;   // (the encoders' activation: plain rcdm_gemm only)
-  if (a.splits <= 1 || (a.epi & RCDM_EPI_GEGLU) || a.dup || a.ph_rows) return RCDM_ESHAPE;
-  GnArgs g{};
-  int rc = rcdm_gn_plan(gn, g);
-  if (rc) return rc;
-  if (!rcdm_gn_three_launch(g)) return RCDM_ESHAPE;
-  if ((long long)g.samples * g.P != a.M || g.C != a.N || gn->ldx != a.ldc) return RCDM_ESHAPE;
-  if (g.CH * g.RPB > 512 || (size_t)(g.CH * g.RPB + g.CH) * 16 * sizeof(float) > 64 * 1024) return RCDM_ESHAPE;   // (the kernel's launch bound; C <= 4096)
-  const size_t need = ((size_t)g.samples * g.splits * g.G * 3 + (size_t)g.samples * g.G * 2) * sizeof(float);
-  if (need_ws) {
-    if (!gn_ws || gn_ws_bytes < need) return RCDM_EWORKSPACE;
-    a.gn_partial = (float*)gn_ws;
-  }
-  a.gn_samples = g.samples; a.gn_P = g.P; a.gn_G = g.G; a.gn_cg = g.cg; a.gn_CH = g.CH; a.gn_RPB = g.RPB;
-  a.gn_splits = g.splits; a.gn_rps = g.rows_per_split;
-  return RCDM_OK;
-}
-
-void from_gemm(const rcdm_gemm_desc* d, IgemmArgs& a) {
-  a.M = d->M; a.N = d->N; a.Cin = d->K; a.Ktot = d->K;
-  a.Hi = a.Wi = a.Ho = a.Wo = 1; a.stride = 1; a.up = 0; a.pad = 1;
-  a.lda = d->lda; a.ldc = d->ldc; a.ldr = d->ldr; a.ldt = d->ldt;
-  a.rows_per_sample = d->rows_per_sample; a.epi = d->epilogue; a.out_scale = d->out_scale;
-  a.dup = (long long)d->dup_rows * d->ldc;
-}
-
-int from_conv(const rcdm_conv3x3_desc* d, IgemmArgs& a) {
-  if (d->stride != 1 && d->stride != 2) return RCDM_ESHAPE;
-  if (d->upsample != 0 && d->upsample != 1) return RCDM_ESHAPE;
-  if (d->n_img <= 0 || d->h_in <= 0 || d->w_in <= 0) return RCDM_EINVAL;
-  const int hv = d->h_in << d->upsample, wv = d->w_in << d->upsample;
-  a.Ho = (hv - 1) / d->stride + 1;
-  a.Wo = (wv - 1) / d->stride + 1;
-  a.Hi = d->h_in; a.Wi = d->w_in; a.stride = d->stride; a.up = d->upsample;
-  if (d->pad_after_only != 0 && d->pad_after_only != 1) return RCDM_ESHAPE;
-  // F.pad(x, (0,1,0,1)) + a stride-2 conv without padding: (h + 1 - 3) / 2 + 1 = h / 2 rows for even h — the same
-  // count as the symmetric form; odd sizes would differ, and the form only exists for stride 2
-  if (d->pad_after_only && (d->stride != 2 || d->upsample || (d->h_in & 1) || (d->w_in & 1))) return RCDM_ESHAPE;
-  a.pad = d->pad_after_only ? 0 : 1;
-  a.M = d->n_img * a.Ho * a.Wo; a.N = d->c_out; a.Cin = d->c_in; a.Ktot = 9 * d->c_in;
-  a.lda = d->lda; a.ldc = d->ldc; a.ldr = d->ldr; a.ldt = d->ldt;
-  a.rows_per_sample = d->rows_per_sample; a.epi = d->epilogue; a.out_scale = d->out_scale;
-  a.dup = (long long)d->dup_rows * d->ldc;
-  if (d->c_in2 < 0) return RCDM_EINVAL;
-  if (d->c_in2 > 0) {   // rcdm_conv3x3_add1x1: a 1x1 convolution of a second input in the same accumulators
-    if (d->stride != 1 || d->upsample || d->pad_after_only) return RCDM_ESHAPE;
-    if ((d->c_in % BK) || (d->c_in2 % BK) || (d->lda2 & 7) || d->lda2 < d->c_in2) return RCDM_ESHAPE;
-    if ((size_t)a.M * (size_t)d->lda2 * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
-    a.Cin2 = d->c_in2; a.lda2 = d->lda2; a.Ktot += d->c_in2;
-  }
-  return RCDM_OK;
-}
-
-// upsample = 2: the nearest-2x upsample + conv3x3 as four 2x2 phase convolutions over the source grid (igemm_args.h,
-// IgemmArgs::ph_rows; weights in the rcdm.h phase layout).  4/9 of the flops of the upsample = 1 form.  Runs on the
-// ping-pong kernel only, unsplit: returns the tile shape, or -1 when the shape does not fill the chip that way (the caller
-// keeps the upsample = 1 form — at the 8x8 -> 16x16 level the plain form with split-K is faster).
-int plan_up2(const rcdm_conv3x3_desc* d, IgemmArgs& a) {
-  if (d->upsample != 2 || d->stride != 1 || d->pad_after_only || d->dup_rows) return -1;
-  if (d->epilogue & ~RCDM_EPI_BIAS) return -1;
-  if (d->n_img <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->c_in <= 0 || d->c_out <= 0 || (d->c_in % BK)) return -1;
-  const long long src = (long long)d->n_img * d->h_in * d->w_in;
-  if (4 * src >= 0x7FFFFFFFll || 4ll * d->c_out * 4 * d->c_in * 2 >= 0x7FFFFFFFll) return -1;   // virtual rows are ints; weight offsets 32-bit
-  a.Hi = a.Ho = d->h_in; a.Wi = a.Wo = d->w_in; a.stride = 1; a.up = 0; a.pad = 1;
-  a.ph_rows = (int)src; a.M = 4 * a.ph_rows; a.N = d->c_out; a.Cin = d->c_in; a.Ktot = 4 * d->c_in;
-  a.lda = d->lda; a.ldc = d->ldc; a.ldr = 0; a.ldt = 0; a.rows_per_sample = 1; a.epi = d->epilogue; a.out_scale = d->out_scale;
-  a.dup = 0;
-  const int cus = num_cus();
-  int best = -1;
-  float best_score = 0.70f;
-  const int forced = (g_force_variant >= kFirstPP && g_force_variant < kFirstPP + kNumPPShapes) ? g_force_variant - kFirstPP : -1;
-  for (int sh = 0; sh < kNumPPShapes; ++sh) {
-    const int bm = kPPShapes[sh].bm, bn = kPPShapes[sh].bn;
-    if (a.ph_rows % bm) continue;
-    const int tm = a.M / bm, tn = (a.N + bn - 1) / bn, tiles = tm * tn;
-    if (forced >= 0) {   // rcdm_set_igemm_variant(6 | 7 | 8): that tile shape whatever the fill (tests)
-      if (sh == forced) best = sh;
-      continue;
-    }
-    const int sp = tiles < cus ? pp_splits(tiles, 4 * (a.Cin / BK)) : 1;   // few tiles (the 8x8 -> 16x16 upsampler): cut K like the plain form does
-    const int work = tiles * sp, rounds = (work + cus - 1) / cus;
-    const float score = ((float)a.N / (float)(tn * bn)) * ((float)work / (float)(rounds * cus)) * (sp > 1 ? 0.90f : 1.0f);
-    if (score > best_score) {
-      best_score = score;
-      best = sh;
-    }
-  }
-  if (best < 0) return -1;
-  a.tilesM = a.M / kPPShapes[best].bm;
-  a.tilesN = (a.N + kPPShapes[best].bn - 1) / kPPShapes[best].bn;
-  a.kc = a.Cin / BK;
-  a.nk = 4 * a.kc;
-  int s = d->split_k > 0 ? d->split_k : (a.tilesM * a.tilesN < cus ? pp_splits(a.tilesM * a.tilesN, a.nk) : 1);
-  if (s > a.nk) s = a.nk;
-  a.nk_per_split = (a.nk + s - 1) / s;
-  a.splits = (a.nk + a.nk_per_split - 1) / a.nk_per_split;
-  return best;
+// the operands of a planned launch, and the checks that need them
+int bind_operands(IgemmArgs& a, const void* A, const void* W, const float* bias, const float* rowvec, const void* residual,
+                  void* out) {
+  a.A = (const f16*)A; a.W = (const f16*)W; a.bias = bias; a.rowvec = rowvec;
+  a.res = (const f16*)residual; a.out = (f16*)out;
+  return check_common(a);
 }
 
 // the plain (upsample 0 | 1) conv launch behind rcdm_conv3x3 / _add1x1 / _gnstat / _add1x1_gnstat; gn: the norm whose
@@ -1468,16 +1013,13 @@ int conv_launch(const rcdm_conv3x3_desc* d, const rcdm_groupnorm_desc* gn, const
                 const float* bias, const float* rowvec, const void* residual, void* out, void* workspace,
                 size_t workspace_bytes, void* gn_workspace, size_t gn_workspace_bytes, void* stream) {
   IgemmArgs a{};
-  int rc = from_conv(d, a);
+  int variant = 0;
+  int rc = plan_conv(d, a, variant);
   if (rc) return rc;
-  a.A = (const f16*)in; a.W = (const f16*)W; a.bias = bias; a.rowvec = rowvec;
-  a.res = (const f16*)residual; a.out = (f16*)out;
   a.A2 = (const f16*)in2;
-  rc = check_common(a);
+  rc = bind_operands(a, in, W, bias, rowvec, residual, out);
   if (rc) return rc;
   if (a.epi & (RCDM_EPI_GEGLU | RCDM_EPI_QUICK_GELU)) return RCDM_ESHAPE;
-  int variant = 0;
-  fill_common(a, d->split_k, &variant);
   if (gn) {
     rc = attach_gnstat(a, gn, gn_workspace, gn_workspace_bytes, true);
     if (rc) return rc;
@@ -1485,39 +1027,16 @@ int conv_launch(const rcdm_conv3x3_desc* d, const rcdm_groupnorm_desc* gn, const
   return launch<9>(a, variant, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// Launch geometry the library chooses for a shape (diagnostics: tools/ceiling.py prices tile quantisation with it): out[8] =
+// {tile variant, BM, BN, row tiles, column tiles, split-K factor, resident blocks per CU of that tile, k-steps of 64}.
+void plan_out(const IgemmArgs& a, int variant, int32_t* out) {
+  out[0] = variant; out[1] = kVariants[variant].bm; out[2] = kVariants[variant].bn; out[3] = a.tilesM; out[4] = a.tilesN;
+  out[5] = a.splits; out[6] = kVariants[variant].blocks_per_cu; out[7] = a.nk;
+}
+
 }  // namespace
 
 extern "C" {
-
-int rcdm_conv3x3_up2_supported(const rcdm_conv3x3_desc* d) {
-  if (!d) return 0;
-  IgemmArgs a{};
-  return plan_up2(d, a) >= 0 ? 1 : 0;
-}
-
-int rcdm_set_igemm_variant(int32_t v) {
-  if (v < -1 || v >= kNumVariants) return RCDM_EINVAL;
-  g_force_variant = v < 0 ? 99 : v;
-  return RCDM_OK;
-}
-
-int rcdm_set_shape_rules(const char* rules) {
-  if (rules && strlen(rules) >= sizeof(g_rules_text)) return RCDM_EINVAL;
-  g_rules_from_api = rules != nullptr;
-  if (rules) strcpy(g_rules_text, rules);
-  g_n_env = -1;   // parsed again at the next launch
-  return RCDM_OK;
-}
-
-int rcdm_set_splitk_slab_f16(int32_t on) {
-  g_slab16 = on < 0 ? -1 : (on ? 1 : 0);
-  return RCDM_OK;
-}
-
-int rcdm_set_igemm_pingpong(int32_t on) {
-  g_pp_mode = on ? 1 : 0;
-  return RCDM_OK;
-}
 
 int rcdm_debug_set_igemm_trace(void* device_buffer) {
   g_trace = (long long*)device_buffer;
@@ -1525,78 +1044,53 @@ int rcdm_debug_set_igemm_trace(void* device_buffer) {
 }
 
 size_t rcdm_gemm_workspace_bytes(const rcdm_gemm_desc* d) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
   IgemmArgs a{};
-  from_gemm(d, a);
-  fill_common(a, d->split_k);
-  return a.splits > 1 ? (size_t)a.splits * a.M * a.N * sizeof(float) : 0;
+  int variant = 0;
+  return plan_gemm(d, PlanFlags{}, a, variant) ? 0 : slab_bytes(a);
 }
 
 size_t rcdm_gemm_lnx_workspace_bytes(const rcdm_gemm_desc* d, int32_t producer, int32_t consumer) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
   IgemmArgs a{};
-  from_gemm(d, a);
-  if (producer) a.stat_out = (float*)16;      // any non-null value: the flags steer the tile choice, nothing is dereferenced
-  if (consumer) a.lnx_stat = (const float*)16;
-  fill_common(a, d->split_k);
-  return a.splits > 1 ? (size_t)a.splits * a.M * a.N * sizeof(float) : 0;
+  int variant = 0;
+  return plan_gemm(d, PlanFlags{producer != 0, consumer != 0}, a, variant) ? 0 : slab_bytes(a);
 }
 
 int rcdm_gemm(const rcdm_gemm_desc* d, const void* A, const void* W, const float* bias, const float* rowvec,
               const void* residual, void* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!d) return RCDM_EINVAL;
   IgemmArgs a{};
-  from_gemm(d, a);
-  a.A = (const f16*)A; a.W = (const f16*)W; a.bias = bias; a.rowvec = rowvec;
-  a.res = (const f16*)residual; a.out = (f16*)out;
-  int rc = check_common(a);
-  if (rc) return rc;
   int variant = 0;
-  fill_common(a, d->split_k, &variant);
+  int rc = plan_gemm(d, PlanFlags{}, a, variant);
+  if (!rc) rc = bind_operands(a, A, W, bias, rowvec, residual, out);
+  if (rc) return rc;
   return launch<1>(a, variant, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int rcdm_gemm_gnstat_ok(const rcdm_gemm_desc* d, const rcdm_groupnorm_desc* gn) {
-  if (!d || !gn || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
   IgemmArgs a{};
-  from_gemm(d, a);
-  fill_common(a, d->split_k);
+  int variant = 0;
+  if (!gn || plan_gemm(d, PlanFlags{}, a, variant)) return 0;
   return attach_gnstat(a, gn, nullptr, 0, false) == RCDM_OK;
 }
 
 int rcdm_gemm_gnstat(const rcdm_gemm_desc* d, const rcdm_groupnorm_desc* gn, const void* A, const void* W, const float* bias,
                      const float* rowvec, const void* residual, void* out, void* workspace, size_t workspace_bytes,
                      void* gn_workspace, size_t gn_workspace_bytes, void* stream) {
-  if (!d) return RCDM_EINVAL;
   IgemmArgs a{};
-  from_gemm(d, a);
-  a.A = (const f16*)A; a.W = (const f16*)W; a.bias = bias; a.rowvec = rowvec;
-  a.res = (const f16*)residual; a.out = (f16*)out;
-  int rc = check_common(a);
-  if (rc) return rc;
   int variant = 0;
-  fill_common(a, d->split_k, &variant);
-  rc = attach_gnstat(a, gn, gn_workspace, gn_workspace_bytes, true);
+  int rc = plan_gemm(d, PlanFlags{}, a, variant);
+  if (!rc) rc = bind_operands(a, A, W, bias, rowvec, residual, out);
+  if (!rc) rc = attach_gnstat(a, gn, gn_workspace, gn_workspace_bytes, true);
   if (rc) return rc;
   return launch<1>(a, variant, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-int rcdm_gemm_stat_parts(const rcdm_gemm_desc* d) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-  IgemmArgs a{};
-  from_gemm(d, a);
-  a.stat_out = (float*)16;   // any non-null value: the tile choice of a statistics-producing launch
-  fill_common(a, d->split_k);
-  return a.splits > 1 ? 0 : a.tilesN;
-}
+int rcdm_gemm_stat_parts(const rcdm_gemm_desc* d) { return rcdm_gemm_lnx_stat_parts(d, 0); }
 
+// the tile choice of a statistics-producing launch; the consumer flag the launch will carry steers it too
 int rcdm_gemm_lnx_stat_parts(const rcdm_gemm_desc* d, int32_t consumer) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
   IgemmArgs a{};
-  from_gemm(d, a);
-  a.stat_out = (float*)16;                       // producer flag, as in rcdm_gemm_stat_parts ...
-  if (consumer) a.lnx_stat = (const float*)16;   // ... and the consumer flag the launch will carry: both steer the tile choice
-  fill_common(a, d->split_k);
+  int variant = 0;
+  if (plan_gemm(d, PlanFlags{true, consumer != 0}, a, variant)) return 0;
   return a.splits > 1 ? 0 : a.tilesN;
 }
 
@@ -1605,10 +1099,8 @@ int rcdm_gemm_lnx(const rcdm_gemm_desc* d, const rcdm_lnx* x, const void* A, con
                   void* stream) {
   if (!d || !x) return RCDM_EINVAL;
   IgemmArgs a{};
-  from_gemm(d, a);
-  a.A = (const f16*)A; a.W = (const f16*)W; a.bias = bias; a.rowvec = rowvec;
-  a.res = (const f16*)residual; a.out = (f16*)out;
-  int rc = check_common(a);
+  from_gemm(d, a);   // (the operand and statistics checks come first, as they always did: plan_gemm fills the shape again)
+  int rc = bind_operands(a, A, W, bias, rowvec, residual, out);
   if (rc) return rc;
   if (a.epi & RCDM_EPI_QUICK_GELU) return RCDM_ESHAPE;
   if (x->stat_out) {
@@ -1625,25 +1117,20 @@ int rcdm_gemm_lnx(const rcdm_gemm_desc* d, const rcdm_lnx* x, const void* A, con
     if (a.lnx_ld < a.M) return RCDM_EINVAL;
     a.lnx_invC = 1.0f / (float)x->C; a.lnx_eps = x->eps;
   }
+  // the flags the launch carries, and a producer's slot count (the caller's, where an LDS-DMA tile has it: rcdm_gemm_lnx_parts_ok)
   int variant = 0;
-  fill_common(a, d->split_k, &variant);
-  if (a.stat_out && a.stat_parts != a.tilesN) {   // the caller's slot count, where an LDS-DMA tile has it (rcdm_gemm_lnx_parts_ok)
-    const int alt = variant_for_parts(a, a.stat_parts);
-    if (alt < 0) return RCDM_ESHAPE;
-    fill_common(a, 1, &variant, alt);             // (a statistics launch is never split)
-  }
+  rc = plan_gemm(d, PlanFlags{a.stat_out != nullptr, a.lnx_stat != nullptr, a.stat_parts}, a, variant);
+  if (rc) return rc;
   return launch<1>(a, variant, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int rcdm_gemm_lnx_parts_ok(const rcdm_gemm_desc* d, int32_t parts, int32_t consumer) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || parts <= 0 || (d->epilogue & RCDM_EPI_GEGLU)) return 0;
+  if (!d || parts <= 0 || (d->epilogue & RCDM_EPI_GEGLU)) return 0;
   IgemmArgs a{};
-  from_gemm(d, a);
-  a.stat_out = (float*)16;
-  if (consumer) a.lnx_stat = (const float*)16;
-  fill_common(a, d->split_k);
-  if (a.splits == 1 && a.tilesN == parts) return 1;
-  return variant_for_parts(a, parts) >= 0;
+  int variant = 0;
+  if (plan_gemm(d, PlanFlags{true, consumer != 0, parts}, a, variant)) return 0;   // no tile has that slot count
+  // (a split plan that has the count: the answer is, as it always was, whether an unsplit LDS-DMA tile has it too)
+  return a.splits == 1 || variant_for_parts(a, parts) >= 0;
 }
 
 int rcdm_gemm_ln(const rcdm_gemm_desc* d, const rcdm_ln_fuse* ln, const void* A, const void* W, const float* bias,
@@ -1652,9 +1139,7 @@ int rcdm_gemm_ln(const rcdm_gemm_desc* d, const rcdm_ln_fuse* ln, const void* A,
   if (ln->pe && (ln->rows_per_frame <= 0 || ln->frames <= 0)) return RCDM_EINVAL;
   IgemmArgs a{};
   from_gemm(d, a);
-  a.A = (const f16*)A; a.W = (const f16*)W; a.bias = bias; a.rowvec = nullptr;
-  a.res = (const f16*)residual; a.out = (f16*)out;
-  int rc = check_common(a);
+  int rc = bind_operands(a, A, W, bias, nullptr, residual, out);
   if (rc) return rc;
   // one 160x320 ping-pong tile must span the output row; only the plain epilogues
   if (a.N > kPPShapes[0].bn || (ln->ld & 7) || d->split_k > 1) return RCDM_ESHAPE;
@@ -1674,61 +1159,46 @@ int rcdm_gemm_ln(const rcdm_gemm_desc* d, const rcdm_ln_fuse* ln, const void* A,
   return rcdm_igemm_pp_launch(a, 1, 0, (hipStream_t)stream);
 }
 
+int rcdm_conv3x3_up2_supported(const rcdm_conv3x3_desc* d) {
+  IgemmArgs a{};
+  int variant = 0;
+  return d && d->upsample == 2 && plan_conv(d, a, variant) == RCDM_OK;
+}
+
 size_t rcdm_conv3x3_workspace_bytes(const rcdm_conv3x3_desc* d) {
   if (!d) return 0;
+  if (d->upsample == 2 && d->c_in2) return 0;   // (no phase form with a second input: every launch entry refuses the pair)
   IgemmArgs a{};
-  if (d->upsample == 2) {
-    if (d->c_in2) return 0;   // (no phase form with a second input: every launch entry refuses the pair)
-    return plan_up2(d, a) >= 0 && a.splits > 1 ? (size_t)a.splits * a.M * a.N * sizeof(float) : 0;
-  }
-  if (from_conv(d, a) || a.Cin <= 0 || a.N <= 0) return 0;
-  fill_common(a, d->split_k);
-  return a.splits > 1 ? (size_t)a.splits * a.M * a.N * sizeof(float) : 0;
+  int variant = 0;
+  return plan_conv(d, a, variant) ? 0 : slab_bytes(a);
 }
 
 int rcdm_conv3x3(const rcdm_conv3x3_desc* d, const void* in, const void* W, const float* bias, const float* rowvec,
                  const void* residual, void* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d) return RCDM_EINVAL;
   if (d->c_in2) return RCDM_EINVAL;   // (a descriptor of rcdm_conv3x3_add1x1 — refused in every form, the phase form included)
-  IgemmArgs a{};
   if (d->upsample == 2) {
-    const int shape = plan_up2(d, a);
-    if (shape < 0) return RCDM_ESHAPE;
+    IgemmArgs a{};
+    int variant = 0;
+    int rc = plan_conv(d, a, variant);
+    if (rc) return rc;
     if (!in || !W || !out || ((a.epi & RCDM_EPI_BIAS) && !bias)) return RCDM_EINVAL;
     if ((a.N & 7) || (a.lda & 7) || (a.ldc & 7) || (size_t)a.ph_rows * (size_t)a.lda * 2 >= 0x7FFFFFFFull) return RCDM_ESHAPE;
     a.A = (const f16*)in; a.W = (const f16*)W; a.bias = bias; a.out = (f16*)out;
     a.trace = nullptr;
     a.dbg = 0;
-    if (a.splits > 1) {
-      if (!workspace || workspace_bytes < (size_t)a.splits * a.M * a.N * sizeof(float)) return RCDM_EWORKSPACE;
-      a.partial = (float*)workspace;
-    }
-    int rc = rcdm_igemm_pp_launch(a, 4, shape, (hipStream_t)stream);
-    if (rc || a.splits == 1) return rc;
-    const size_t total = (size_t)a.M * (a.N / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return rcdm_check_launch();
+    rc = bind_slabs(a, workspace, workspace_bytes);
+    if (rc) return rc;
+    // (a phase launch has no GEGLU, no quick-GELU and no gn_partial: the plain reduce kernel over M x N / 8 threads)
+    return reduce_if_split(rcdm_igemm_pp_launch(a, 4, variant - kVarPP, (hipStream_t)stream), a, (hipStream_t)stream);
   }
   return conv_launch(d, nullptr, in, nullptr, W, bias, rowvec, residual, out, workspace, workspace_bytes, nullptr, 0, stream);
 }
 
-// Launch geometry the library chooses for a shape (diagnostics: tools/ceiling.py prices tile quantisation with it): out[8] =
-// {tile variant, BM, BN, row tiles, column tiles, split-K factor, resident blocks per CU of that tile, k-steps of 64}.
-static void plan_out(const IgemmArgs& a, int variant, int32_t* out) {
-  out[0] = variant; out[1] = kTiles[variant].bm; out[2] = kTiles[variant].bn; out[3] = a.tilesM; out[4] = a.tilesN;
-  out[5] = a.splits; out[6] = kTiles[variant].blocks_per_cu; out[7] = a.nk;
-}
-
 int rcdm_gemm_plan_query(const rcdm_gemm_desc* d, int32_t producer, int32_t consumer, int32_t* out8) {
-  if (!d || !out8 || d->M <= 0 || d->N <= 0 || d->K <= 0) return RCDM_EINVAL;
   IgemmArgs a{};
-  from_gemm(d, a);
-  if (producer) a.stat_out = (float*)16;
-  if (consumer) a.lnx_stat = (const float*)16;
   int variant = 0;
-  fill_common(a, d->split_k, &variant);
+  if (!out8 || plan_gemm(d, PlanFlags{producer != 0, consumer != 0}, a, variant)) return RCDM_EINVAL;
   plan_out(a, variant, out8);
   return RCDM_OK;
 }
@@ -1736,15 +1206,8 @@ int rcdm_gemm_plan_query(const rcdm_gemm_desc* d, int32_t producer, int32_t cons
 int rcdm_conv3x3_plan_query(const rcdm_conv3x3_desc* d, int32_t* out8) {
   if (!d || !out8) return RCDM_EINVAL;
   IgemmArgs a{};
-  if (d->upsample == 2) {
-    const int shape = plan_up2(d, a);
-    if (shape < 0) return RCDM_ESHAPE;
-    plan_out(a, kFirstPP + shape, out8);
-    return RCDM_OK;
-  }
-  if (from_conv(d, a) || a.Cin <= 0 || a.N <= 0) return RCDM_EINVAL;
   int variant = 0;
-  fill_common(a, d->split_k, &variant);
+  if (plan_conv(d, a, variant)) return d->upsample == 2 ? RCDM_ESHAPE : RCDM_EINVAL;
   plan_out(a, variant, out8);
   return RCDM_OK;
 }
@@ -1759,8 +1222,8 @@ int rcdm_conv3x3_add1x1(const rcdm_conv3x3_desc* d, const void* in, const void* 
 int rcdm_conv3x3_gnstat_ok(const rcdm_conv3x3_desc* d, const rcdm_groupnorm_desc* gn) {
   if (!d || !gn || d->upsample == 2) return 0;
   IgemmArgs a{};
-  if (from_conv(d, a) || a.Cin <= 0 || a.N <= 0) return 0;
-  fill_common(a, d->split_k);
+  int variant = 0;
+  if (plan_conv(d, a, variant)) return 0;
   return attach_gnstat(a, gn, nullptr, 0, false) == RCDM_OK;
 }
 

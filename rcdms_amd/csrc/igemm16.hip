@@ -15,7 +15,7 @@
 // pieces per wave and step, XOR swizzle on the source side as in igemm.hip); the pieces of step g+1 are issued right
 // after the barrier that opens step g.  One tile per block, XCD-aware tile order; epilogue through igemm_epilogue.h.
 #include "common.h"
-#include "igemm_args.h"
+#include "igemm_plan.h"
 #include "pp_sync.h"
 #include "igemm_epilogue.h"
 #ifndef RCDM_I16_ABLATE
@@ -232,6 +232,7 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
 }
 
 constexpr int kLds16 = 2 * (160 + 160) * 128;  // 81920 B >= the 160 x (320 + 16) B staging tile
+static_assert(kLds16 == kVariants[kVar160].lds_bytes(), "the planner's variant table disagrees");
 
 template <int TAPS>
 int launch16(const IgemmArgs& a, hipStream_t stream) {

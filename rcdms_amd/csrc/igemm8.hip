@@ -33,11 +33,9 @@
 // Pieces that do not divide over 4 waves (BM/2 = 80 rows = 10 pieces: waves 0,1 issue 3, waves 2,3 issue 2) make the
 // vmcnt immediates wave-dependent: picked by a wave-uniform branch.
 #include "common.h"
-#include "igemm_args.h"
+#include "igemm_plan.h"
 #include "pp_sync.h"
 #include "igemm_epilogue.h"
-
-const PPShape kPPShapes[kNumPPShapes] = {{160, 320}, {160, 256}, {256, 256}};
 
 // cache policy of the two LDS-DMA streams (buffer_load ... lds aux bits: 1 = sc0, 2 = nt, 16 = sc1); experiments only
 #ifndef RCDM_PP_AAUX
@@ -399,6 +397,9 @@ constexpr int pp_lds_bytes() {
   constexpr int ring = (2 * BM + 3 * BN) * 128, stage = BM * (2 * BN + 16);
   return ring > stage ? ring : stage;
 }
+
+static_assert(pp_lds_bytes<5, 5>() == kVariants[kVarPP].lds_bytes() && pp_lds_bytes<5, 4>() == kVariants[kVarPP + 1].lds_bytes() &&
+              pp_lds_bytes<8, 4>() == kVariants[kVarPP256].lds_bytes(), "the planner's variant table disagrees");
 
 template <int TAPS, int FMW, int FNW>
 int launch_pp(const IgemmArgs& a, hipStream_t stream) {

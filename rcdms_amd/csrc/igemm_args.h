@@ -26,7 +26,7 @@ struct IgemmArgs {
   long long dup;     // element offset of the second copy of every output row (0 = none): dup_rows * ldc
   int tilesM, tilesN, kc, nk, splits, nk_per_split;
   long long* trace;  // debug: per-block s_memtime stamps (rcdm_debug_set_igemm_trace), normally null
-  int dbg;           // ping-pong loop switches: 8 = rotate the k order per block (RCDM_PP_ROTATE, default on)
+  int dbg;           // ping-pong loop switches: 8 = rotate the k order per block (RCDM_PP_ROTATE, default off)
   // fused LayerNorm of the output rows (rcdm_gemm_ln; kEpiLN in epi, the 160x320 ping-pong tile only)
   const float* ln_g;
   const float* ln_b;
@@ -84,7 +84,7 @@ constexpr int kEpiLN = 1 << 20;  // internal epilogue bit (not part of the C-ABI
 constexpr int kGegluGroup = 16;
 __host__ __device__ __forceinline__ int geglu_out_col(int n) { return (n >> 5) * 16 + (n & 15); }
 
-// igemm8.hip: ping-pong tile shapes (index into kPPShapes), launched by igemm.hip's dispatcher
+// igemm8.hip: ping-pong tile shapes (index into kPPShapes, defined with the planner's variant table: igemm_plan.hip), launched by igemm.hip's dispatcher
 struct PPShape { int bm, bn; };
 constexpr int kNumPPShapes = 3;
 extern const PPShape kPPShapes[kNumPPShapes];

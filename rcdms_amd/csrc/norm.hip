@@ -607,16 +607,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const f16* __restrict
 }
 
 bool gn_single_launch(const GnArgs& a) {
-  static int fused_mode = -1;  // RCDM_GN_FUSED=0: three-launch form everywhere (A/B switch)
-  if (fused_mode < 0) {
-    const char* e = getenv("RCDM_GN_FUSED");
-    fused_mode = e ? atoi(e) : 1;
-  }
-  static int fused_rows = -1;  // RCDM_GN_FUSED_ROWS: rows per sample up to which the single-launch form is used
-  if (fused_rows < 0) {
-    const char* e = getenv("RCDM_GN_FUSED_ROWS");
-    fused_rows = e ? atoi(e) : 512;
-  }
+  static const int fused_mode = rcdm_env_int("RCDM_GN_FUSED", 1);  // RCDM_GN_FUSED=0: three-launch form everywhere (A/B switch)
+  static const int fused_rows = rcdm_env_int("RCDM_GN_FUSED_ROWS", 512);  // RCDM_GN_FUSED_ROWS: rows per sample up to which the single-launch form is used
   const int gb = gn_fused_bundle(a.G, a.cg);
   // one block per (sample, bundle) pays up to a few hundred rows per sample (measured: 15 -> 9 us at 320 rows, but
   // 17 -> 22 us at 1280 and 25 -> 64 us at 4096: a single block streams its slab too slowly)
@@ -630,10 +622,7 @@ int gn_finalize_apply(GnArgs& a, hipStream_t stream) {
   // of a 32x32-level per-frame norm each pay a partials round trip + eight butterflies, more than the 4.9 us launch they replace.
   // RCDM_GN_FOLD=1 / rcdm_set_groupnorm_fold(1) turns it on (bit-identical results).
   int& fold_mode = g_gn_fold_mode;
-  if (fold_mode < 0) {
-    const char* e = getenv("RCDM_GN_FOLD");
-    fold_mode = e ? atoi(e) : 0;
-  }
+  if (fold_mode < 0) fold_mode = rcdm_env_int("RCDM_GN_FOLD", 0);
   const int threads64 = (threads + 63) / 64 * 64;
   const bool fold = fold_mode && a.samples >= 4 && a.splits <= 128 && a.G <= 64 && threads64 <= 1024;
   if (!fold) {
@@ -816,11 +805,7 @@ int rcdm_layernorm(const rcdm_layernorm_desc* d, const void* x, const float* gam
   const int nchunks = d->C >> 3;
   dim3 block(256);
   const int rpf = pe ? d->rows_per_frame : 1, fr = pe ? d->frames : 1;
-  static int wave_rows = -1;  // RCDM_LN_WAVEROW=1: the round-1 wave-per-row kernel (A/B switch)
-  if (wave_rows < 0) {
-    const char* e = getenv("RCDM_LN_WAVEROW");
-    wave_rows = e ? atoi(e) : 0;
-  }
+  static const int wave_rows = rcdm_env_int("RCDM_LN_WAVEROW", 0);  // RCDM_LN_WAVEROW=1: the round-1 wave-per-row kernel (A/B switch)
   if (!wave_rows) {
     const int lpr = nchunks <= 40 ? 8 : nchunks <= 80 ? 16 : nchunks <= 160 ? 32 : 64;
     const int cpl = (nchunks + lpr - 1) / lpr;

@@ -5,6 +5,19 @@
 
 thread_local int g_rcdm_last_hip_error = 0;
 
+int rcdm_num_cus() {
+  static int cus = 0;
+  if (cus <= 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      cus = n;
+    else
+      cus = 256;
+  }
+  return cus;
+}
+
 namespace {
 // Roofline calibration (tools/mfma_peak.py): nothing but independent v_mfma_f32_32x32x16_f16 chains on every SIMD —
 // the sustained dense-f16 matrix rate this part reaches under full matrix load, and the s_memtime tick rate.

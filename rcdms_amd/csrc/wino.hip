@@ -508,18 +508,6 @@ __global__ __launch_bounds__(256) void upsample_gather_kernel(const UpGatherArgs
   *(uint4*)(p.out + (size_t)o * p.ldc + c8 * 8) = q.u;
 }
 
-int g_wino_cus = 0;
-int wino_cus() {
-  if (g_wino_cus <= 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      g_wino_cus = n;
-    else
-      g_wino_cus = 256;
-  }
-  return g_wino_cus;
-}
-
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // geometry + workspace carve-up; returns an RCDM_* code
@@ -554,7 +542,7 @@ int wino_plan(const rcdm_conv3x3_desc* d, WinoArgs& a) {
   int splits = d->split_k;
   if (splits <= 0) {
     const int blocks = a.E * a.tilesM * a.tilesN;
-    splits = wino_cus() / (blocks > 0 ? blocks : 1);
+    splits = rcdm_num_cus() / (blocks > 0 ? blocks : 1);
     if (splits > a.nk / 5) splits = a.nk / 5;
     if (splits > 8) splits = 8;
   }
@@ -572,10 +560,7 @@ size_t wino_slab_bytes(const WinoArgs& a) { return align256((size_t)a.E * a.spli
 // before the output transform), 0: fp32 slabs.  -1 = not set: environment RCDM_WINO_SLAB16, default 1 (measured: -10 us per 16x16-level conv, whole-UNet rel-RMS +0.2 ... +2.7 %).
 int g_wino_slab16 = -1;
 int wino_slab16() {
-  if (g_wino_slab16 < 0) {
-    const char* e = getenv("RCDM_WINO_SLAB16");
-    g_wino_slab16 = e ? (atoi(e) != 0) : 1;
-  }
+  if (g_wino_slab16 < 0) g_wino_slab16 = rcdm_env_int("RCDM_WINO_SLAB16", 1) != 0;
   return g_wino_slab16;
 }
 

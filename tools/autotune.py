@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Sweep tile variant x split-K factor for every distinct GEMM / conv3x3 shape of the bench workload's launch plan and
-report where the library's shape heuristic (pick_variant / plan_splits, igemm.hip) is not the fastest choice.
+report where the library's shape heuristic (pick_variant / plan_splits, igemm_plan.hip) is not the fastest choice.
 Every candidate is timed back to back with HIP events on the plan's own shapes (synthetic operands); the in-graph times
 are 5-15 % higher (operands HBM-cold) but rank the same.   usage: python tools/autotune.py [--latent 64] [--min-gain 0.05]"""
 import argparse
