@@ -710,6 +710,49 @@ typedef struct {
 int rcdm_frames_to_u8(const rcdm_frames_u8_desc* d, const void* src, void* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG: n equally sized uint8 RGB images on the device (HWC, src_pitch bytes between rows, src_stride between images — the
+ * buffers rcdm_frames_to_u8 writes, the cells of a grid included) -> n complete PNG files in device memory + their sizes.
+ * What the driver does per story with PIL.Image.save (stage2_batchtest_rcdms_model.py:378-401).  The files are plain PNG
+ * (8-bit, colour type 2, no interlace, no ancillary chunks) that any decoder reads; the deflate stream is LITERALS ONLY:
+ *   filter     per scanline with bpp = 3, the row above the first row is zeros.  RCDM_PNG_ADAPTIVE: all five filters (None,
+ *              Sub, Up, Average, Paeth) are tried, cost = sum over the row's bytes of (v < 128 ? v : 256 - v), the smallest
+ *              cost wins, the lowest filter number on a tie.  filter = 0..4: that filter for every row.
+ *   blocks     the filtered stream of an image, h * (1 + 3 w) bytes, is cut every RCDM_PNG_BLOCK bytes regardless of rows.
+ *              Each cut is one dynamic-Huffman block (BFINAL 0) over 256 literals + end-of-block: HLIT 257, HDIST 1 with
+ *              the one distance length 0, HCLEN 19, code-length code fixed (symbols 0..15: 4 bits, 16..18 unused), so the
+ *              header is 1103 bits behind the 3 block-type bits.  Behind its end-of-block code comes an empty stored block
+ *              (3 bits, pad to a byte, 00 00 FF FF) whose BFINAL is 1 behind the image's last block only.
+ *   code       Huffman over the block's histogram, end-of-block counting 1, by the two-queue construction: leaves ascending
+ *              by (count, symbol index); internal nodes in creation order; the leaf queue wins a tie.  If the tree is deeper
+ *              than 15 every non-zero count becomes (c + 1) >> 1 and it is rebuilt, until it fits.  Canonical codes (RFC 1951
+ *              3.2.2).  A block of one distinct byte gets length 1 for it and for end-of-block.
+ *   container  signature, IHDR, one IDAT per block — the first starts with the zlib header 78 01, the last ends with the
+ *              Adler-32 of the whole filtered stream —, IEND; every chunk with its CRC-32.
+ * No match search: a file is never smaller than 1 bit per filtered byte (h (1 + 3 w) / 8 bytes), so flat images come out
+ * many times larger than zlib's; on noisy decoder-like frames the size is about Pillow's default.
+ *   rcdm_png_bound            worst-case bytes of ONE file (0 for a descriptor the entry point refuses); dst_stride >= it
+ *   rcdm_png_workspace_bytes  filtered streams + one RCDM_PNG_SLOT-byte slot and one 16-byte record per block
+ *   rcdm_png_encode           three launches on `stream`, no host readback: file i lies at dst + i * dst_stride, its length in
+ *                             sizes[i] (device memory, 8-byte aligned); bytes of the stream's slot past sizes[i] are not
+ *                             written.  workspace: 16-byte aligned, read and written; src is only read.
+ * RCDM_EINVAL: null pointers, src_pitch < 3 w, negative src_stride, dst_stride < rcdm_png_bound when n > 1, channels != 3,
+ * a filter outside -1..4, n < 1, a misaligned workspace / sizes.  RCDM_ESHAPE: a side outside 1..8192, n > 65535.  All
+ * checked before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_PNG_BLOCK 32768
+#define RCDM_PNG_SLOT 41728
+#define RCDM_PNG_ADAPTIVE (-1)
+typedef struct {
+  int64_t src_pitch, src_stride;   /* bytes between source rows / source images */
+  int64_t dst_stride;              /* bytes between output files */
+  int32_t n, h, w, channels;       /* channels == 3 */
+  int32_t filter;                  /* RCDM_PNG_ADAPTIVE or 0..4 */
+} rcdm_png_desc;
+size_t rcdm_png_bound(const rcdm_png_desc* d);
+size_t rcdm_png_workspace_bytes(const rcdm_png_desc* d);
+int rcdm_png_encode(const rcdm_png_desc* d, const void* src, void* workspace, void* dst, uint64_t* sizes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

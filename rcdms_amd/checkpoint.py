@@ -4,7 +4,7 @@ The reference's driver (stage2_batchtest_rcdms_model.py) reads ONE DeepSpeed fil
 `./stage2/<exp>/<weights_number>/mp_rank_00_model_states.pt`, takes its `"module"` dict and routes keys by prefix
 (:225-243): `unet.*` -> the UNet3D, `seen_module.*` -> fine_stack (local_module), `unseen_module.*` -> semantic_stack
 (global_module); anything else is printed and dropped.  These helpers restate that routing (with the errors made explicit instead of printed), the story
-sharding across ranks (`split_list`, :58-70), the PNG grid writer (`image_grid`, :79-93) and the ARLDM h5 test-split reader
+sharding across ranks (`split_list`, :58-70), the PNG grid writer (`image_grid`, :79-93; `story_grid_png`: the same grid encoded on the device) and the ARLDM h5 test-split reader
 (`read_story_split` / `pick_story_frames`, :41-56,440-453,257-266), so a maintainer's script keeps its file formats when it
 switches to `rcdms_amd`."""
 import os
@@ -73,6 +73,28 @@ def split_list(n, m):
         out.append(list(range(start, end)))
         start = end
     return out
+
+
+def story_grid_png(cells, rows, cols):
+    """The driver's comparison grid (:79-93, 378-401) as a PNG file without the host: `cells` — rows * cols device uint8
+    frames (h, w, 3) of one size, a list or one (rows * cols, h, w, 3) tensor, row-major as image_grid pastes them — are
+    copied on the device into one (rows * h, cols * w, 3) grid (a row-strided copy per cell) and encoded there
+    (rcdms_amd.image.encode_png: literal-only deflate, see include/rcdm.h "PNG").  -> the file as `bytes`."""
+    from .image import encode_png
+    cells = list(cells) if not isinstance(cells, torch.Tensor) else list(cells.unbind(0))
+    if len(cells) != rows * cols or not cells:
+        raise AssertionError(f"{len(cells)} images do not fill a {rows} x {cols} grid")
+    first = cells[0]
+    for c in cells:
+        if not isinstance(c, torch.Tensor) or not c.is_cuda or c.dtype != torch.uint8 or c.dim() != 3 or c.shape != first.shape or c.shape[2] != 3:
+            raise ValueError("story_grid_png takes device uint8 (h, w, 3) cells of one size (frames of output_type=\"uint8\" / "
+                             "frames_to_uint8); image_grid is the host path for anything else")
+    h, w, _ = first.shape
+    grid = torch.empty(rows * h, cols * w, 3, dtype=torch.uint8, device=first.device)
+    for i, c in enumerate(cells):
+        r, k = divmod(i, cols)
+        grid[r * h:(r + 1) * h, k * w:(k + 1) * w].copy_(c)
+    return encode_png(grid)[0]
 
 
 def image_grid(imgs, rows, cols):

@@ -94,6 +94,12 @@ class FramesU8Desc(C.Structure):
                 ("channels", C.c_int32), ("src_kind", C.c_int32), ("ld", C.c_int32)]
 
 
+class PngDesc(C.Structure):
+    _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("n", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32)]
+
+
+PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
 IMAGE_TILE = 32                                         # RCDM_IMAGE_TILE
 IMAGE_U8, IMAGE_F32_NCHW, IMAGE_F16_ROWS = 0, 1, 2      # ResampleDesc.mode
 FRAMES_F16_ROWS, FRAMES_F32_NCHW = 0, 1                 # FramesU8Desc.src_kind
@@ -165,6 +171,9 @@ SYMBOLS = {
     "rcdm_image_resample_lds_bytes": (_SZ, [C.POINTER(ResampleDesc)]),
     "rcdm_image_resample": (C.c_int, [C.POINTER(ResampleDesc), _P, _P, _P, _P, _P, _P, _P]),
     "rcdm_frames_to_u8": (C.c_int, [C.POINTER(FramesU8Desc), _P, _P, _P]),
+    "rcdm_png_bound": (_SZ, [C.POINTER(PngDesc)]),
+    "rcdm_png_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
+    "rcdm_png_encode": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -489,6 +498,19 @@ def image_resample(desc, src, kx, bx, ky, by, dst, stream=None):
 
 def frames_to_u8(desc, src, dst, stream=None):
     _check(load().rcdm_frames_to_u8(C.byref(desc), src, dst, stream_ptr() if stream is None else stream), "rcdm_frames_to_u8")
+
+
+def png_bound(desc):
+    return int(load().rcdm_png_bound(C.byref(desc)))
+
+
+def png_workspace_bytes(desc):
+    return int(load().rcdm_png_workspace_bytes(C.byref(desc)))
+
+
+def png_encode(desc, src, workspace, dst, sizes, stream=None):
+    _check(load().rcdm_png_encode(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
+           "rcdm_png_encode")
 
 
 def assemble_input(lat, mask, masked, S, reps, frames, H, W, out, ld, c_pad, stream=None):

@@ -11,6 +11,8 @@ arithmetic on coefficient tables of 22 fractional bits; `resample_tables` builds
 exactly as Pillow does and the kernel does the integer multiply-accumulate, so the resized bytes equal Pillow's bit for bit.
 Back end — RCDMs_pipeline.py:274-287 and the driver's tensor2list: `frames_to_uint8` is (x / 2 + 0.5).clamp(0, 1) * 255
 truncated, from the VAE decoder's f16 rows or an fp32 NCHW tensor straight to uint8 HWC (rcdm_frames_to_u8).
+Files — the driver's PIL.Image.save calls (:378-401): `encode_png` / `save_png` / `PngEncoder` turn device uint8 frames into
+complete PNG files on the device (rcdm_png_encode: adaptive filters, literal-only Huffman deflate), one download per call.
 
 No CPU path: a call without a GPU raises (only `resample_tables` and the geometry helpers are host code)."""
 import math
@@ -332,3 +334,125 @@ def frames_to_uint8(x, out=None):
     if keep is not None:
         keep.record_stream(torch.cuda.current_stream(device))
     return out.view(*lead, H, W, 3) if lead is not None and out.is_contiguous() else out
+
+
+# ------------------------------------------------------------------------------------------------
+# PNG files of uint8 frames (rcdm_png_encode): what the driver's PIL.Image.save calls write, encoded on the device
+PNG_FILTERS = {"adaptive": hip.PNG_ADAPTIVE, "none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4}
+
+
+def _png_filter(f):
+    v = PNG_FILTERS.get(f.lower()) if isinstance(f, str) else (int(f) if isinstance(f, int) and not isinstance(f, bool) else None)
+    if v is None or not -1 <= v <= 4:
+        raise ValueError(f"png filter {f!r}: one of {sorted(PNG_FILTERS)} or -1..4")
+    return v
+
+
+def _png_frames(frames):
+    """-> the (n, h, w, 3) device uint8 view the kernel reads (dense pixels, any row pitch / image stride)."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"PNG frames are a device uint8 tensor, got {type(frames).__name__}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"PNG frames are uint8, got {frames.dtype}: convert with frames_to_uint8 first")
+    if frames.dim() not in (3, 4) or frames.shape[-1] != 3 or 0 in frames.shape:
+        raise ValueError(f"PNG frames are (h, w, 3) or (n, h, w, 3), got {tuple(frames.shape)}")
+    if not frames.is_cuda:
+        raise hip.RcdmError("encode_png runs on the HIP path only: frames must be a device tensor (there is no CPU encoder here)")
+    t = frames if frames.dim() == 4 else frames.unsqueeze(0)
+    n, h, w, _ = t.shape                                 # the stride of a dimension of size 1 addresses nothing: any value goes
+    if t.stride(3) != 1 or (w > 1 and t.stride(2) != 3) or (h > 1 and t.stride(1) < 3 * w) or (n > 1 and t.stride(0) < 0):
+        t = t.contiguous()
+    return t
+
+
+def _png_device(device):
+    """`device` with its index spelled out ("cuda" -> the current device), so that it compares equal to a tensor's."""
+    if device is None:
+        return _default_device()
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+class PngEncoder:
+    """n images of h x w on one device: the descriptor's geometry, the workspace, the output streams (+ their sizes behind
+    them, so one download brings both) and a pinned host buffer of the same size, kept for every call of this shape."""
+
+    def __init__(self, h, w, n=1, device=None):
+        self.device = _png_device(device)
+        self.h, self.w, self.n = int(h), int(w), int(n)
+        d = self._desc(3 * self.w, 0, 0, hip.PNG_ADAPTIVE)
+        self.bound = hip.png_bound(d)
+        if self.bound == 0:
+            raise hip.RcdmError(f"rcdm_png_encode takes 1..65535 images with sides 1..8192, got {self.n} of {self.h}x{self.w}")
+        self.stride = (self.bound + 15) & ~15
+        self.workspace = torch.empty(hip.png_workspace_bytes(d), dtype=torch.uint8, device=self.device)
+        self.out = torch.empty(self.n * self.stride + 8 * self.n, dtype=torch.uint8, device=self.device)
+        self.host = torch.empty(self.out.shape, dtype=torch.uint8, pin_memory=True)
+
+    def _desc(self, pitch, src_stride, dst_stride, filt):
+        return hip.PngDesc(pitch, src_stride, dst_stride, self.n, self.h, self.w, 3, filt)
+
+    def launch(self, frames, filter="adaptive", dst=None, dst_stride=None, sizes=None):
+        """The launch sequence alone (graph-capturable): files at dst + i * dst_stride, sizes[i] (uint64) on the device.
+        Default destination: this encoder's own buffer."""
+        t = _png_frames(frames)
+        if tuple(t.shape) != (self.n, self.h, self.w, 3) or t.device != self.device:
+            raise ValueError(f"this encoder takes ({self.n}, {self.h}, {self.w}, 3) on {self.device}, got {tuple(t.shape)} on {t.device}")
+        dst_ptr = self.out.data_ptr() if dst is None else dst
+        stride = self.stride if dst_stride is None else int(dst_stride)
+        sizes_ptr = self.out.data_ptr() + self.n * self.stride if sizes is None else sizes
+        d = self._desc(t.stride(1) if self.h > 1 else 3 * self.w, t.stride(0) if self.n > 1 else 0, stride if self.n > 1 else 0,
+                       _png_filter(filter))
+        hip.png_encode(d, t.data_ptr(), self.workspace.data_ptr(), dst_ptr, sizes_ptr)
+        return t
+
+    def encode(self, frames, filter="adaptive"):
+        """-> list of n `bytes`: one launch sequence, one download, a slice per file."""
+        keep = self.launch(frames, filter)
+        self.host.copy_(self.out, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        del keep
+        raw = self.host.numpy()
+        sizes = raw[self.n * self.stride:].view(np.uint64)
+        out = []
+        for i in range(self.n):
+            size = int(sizes[i])
+            if not 57 <= size <= self.bound:
+                raise hip.RcdmError(f"rcdm_png_encode reported {size} bytes for image {i} (bound {self.bound})")
+            out.append(raw[i * self.stride:i * self.stride + size].tobytes())
+        return out
+
+
+_PNG_ENCODERS = {}
+
+
+def png_encoder(h, w, n=1, device=None):
+    device = _png_device(device)
+    key = (int(h), int(w), int(n), device)
+    e = _PNG_ENCODERS.get(key)
+    if e is None:
+        e = _PNG_ENCODERS[key] = PngEncoder(h, w, n, device)
+    return e
+
+
+def encode_png(frames, filter="adaptive"):
+    """Device uint8 frames (n, h, w, 3) or (h, w, 3), dense pixels with any row pitch / image stride -> list of PNG files as
+    `bytes`.  Literal-only deflate (see include/rcdm.h, "PNG"): about Pillow's default size on noisy decoder output, far
+    larger than Pillow's on flat images.  filter: "adaptive" (per row) or one of none / sub / up / average / paeth."""
+    _png_filter(filter)
+    t = _png_frames(frames)
+    return png_encoder(t.shape[1], t.shape[2], t.shape[0], t.device).encode(t, filter)
+
+
+def save_png(paths, frames):
+    """Write frames[i] to paths[i] (a single path for a single (h, w, 3) frame)."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    files = encode_png(frames)
+    if len(files) != len(paths):
+        raise ValueError(f"{len(paths)} paths for {len(files)} frames")
+    for p, b in zip(paths, files):
+        with open(p, "wb") as f:
+            f.write(b)

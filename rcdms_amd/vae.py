@@ -157,6 +157,12 @@ class AutoencoderKLDecoder(nn.Module):
             raise hip.RcdmError(f"AutoencoderKLDecoder runs on the HIP path only (module is on {self.device})")
         return self._decode_program(z).forward_uint8(z)
 
+    @torch.no_grad()
+    def decode_png(self, z, filter="adaptive"):
+        """z (n, 4, h, w) -> n PNG files as `bytes`: decode_uint8, then rcdm_png_encode on those frames (image.encode_png)."""
+        from .image import encode_png
+        return encode_png(self.decode_uint8(z), filter)
+
 
 class DiagonalGaussianDistribution:
     """`encode(x).latent_dist`: mean / logvar (clamped to [-30, 20]) of the posterior, as diffusers' class of this name."""

@@ -314,8 +314,13 @@ class RCDMsPipeline:
             if callback is None:
                 bar.update(num_inference_steps)
 
-        if output_type == "uint8":
+        if output_type in ("uint8", "png"):
             video = self.decode_latents_uint8(final.to(text_embeddings.dtype))
+            if output_type == "png":                       # [[bytes] * f] * b: one PNG file per frame, encoded on the device
+                from rcdms_amd.image import encode_png
+                b, f = video.shape[:2]
+                files = encode_png(video.reshape(b * f, *video.shape[2:]))
+                video = [files[i * f:(i + 1) * f] for i in range(b)]
             return RCDMsPipelineOutput(videos=video) if return_dict else video
         video = self.decode_latents(final.to(text_embeddings.dtype))
         if output_type == "tensor":
