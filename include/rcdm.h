@@ -753,6 +753,39 @@ size_t rcdm_png_workspace_bytes(const rcdm_png_desc* d);
 int rcdm_png_encode(const rcdm_png_desc* d, const void* src, void* workspace, void* dst, uint64_t* sizes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG, match mode: the same descriptor, the same files except for what a block's dynamic-Huffman block holds — (length,
+ * distance) pairs where the filtered stream repeats itself at one of a few fixed distances.  Opt-in; rcdm_png_encode and its
+ * bytes are unchanged.  Filtering, the cut every RCDM_PNG_BLOCK filtered bytes, one IDAT per block, the empty stored block
+ * behind each, the zlib header, Adler-32 and the container are those of "PNG" above.  With S = 1 + 3 w (a filtered row) and
+ * a block [b0, b1) of the image's stream s:
+ *   candidates  at position i the distances 1, 2, 3, 4, 6, 9, 12, S - 3, S, S + 3, 2 S, in this order; d is dropped if d < 1,
+ *               d > 32768 or d > i.  The source may lie in front of b0, in the image's earlier bytes, never in another
+ *               image's.  (For w <= 2 a distance occurs twice; that changes nothing.)
+ *   length      of candidate d: the count of k >= 0 with s[i + k] == s[i + k - d], capped at 258 and at b1 - i — a match never
+ *               crosses the cut.  The longest candidate is the position's match, the earlier one in the list on a tie; it
+ *               is usable from length 4.
+ *   parse       greedy from b0: a usable match at i emits (length, distance) and continues at i + length, otherwise the
+ *               literal s[i] and i + 1.
+ *   match form  a dynamic-Huffman block with HLIT 286, HDIST 30, HCLEN 19 and the same fixed 4-bit code-length code: a
+ *               header of 3 + 5 + 5 + 4 + 57 + 316 * 4 = 1338 bits.  Literal / length code over 286 symbols (end-of-block
+ *               counts 1), distance code over 30, each by the two-queue construction of "PNG" with its tie rules and its
+ *               (c + 1) >> 1 limiter on its own counts; canonical codes.  ONE used distance symbol gets length 1 (RFC 1951
+ *               3.2.7).  Length and distance extra bits as in RFC 1951 3.2.5 (length 258 is symbol 285).
+ *   fallback    the block's bits in match form, up to and including the end-of-block code, are compared with its bits in the
+ *               literal form of "PNG"; the match form is taken only if it is STRICTLY smaller, otherwise the block's bytes
+ *               are exactly rcdm_png_encode's.
+ * So every block is <= its literal-only size — rcdm_png_bound and RCDM_PNG_SLOT hold for both modes — and a file whose
+ * blocks all fall back is byte-identical to rcdm_png_encode's.  There is no hash search and no lazy matching: a flat 256 x
+ * 256 cartoon comes out at 0.29 of its literal-only size, 0.85 of zlib level 1's and 1.7 of zlib level 6's on the same stream.
+ *   rcdm_png_match_workspace_bytes  the workspace of rcdm_png_encode_match (today the same number as rcdm_png_workspace_bytes)
+ *   rcdm_png_encode_match           as rcdm_png_encode: three launches on `stream` (filter, match block, assemble), no host
+ *                                   readback, the same layout of dst / sizes, the same alignment rules
+ * Argument checks and error codes are those of rcdm_png_encode, all before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rcdm_png_match_workspace_bytes(const rcdm_png_desc* d);
+int rcdm_png_encode_match(const rcdm_png_desc* d, const void* src, void* workspace, void* dst, uint64_t* sizes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

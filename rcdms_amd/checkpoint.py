@@ -75,11 +75,12 @@ def split_list(n, m):
     return out
 
 
-def story_grid_png(cells, rows, cols):
+def story_grid_png(cells, rows, cols, match=False):
     """The driver's comparison grid (:79-93, 378-401) as a PNG file without the host: `cells` — rows * cols device uint8
     frames (h, w, 3) of one size, a list or one (rows * cols, h, w, 3) tensor, row-major as image_grid pastes them — are
     copied on the device into one (rows * h, cols * w, 3) grid (a row-strided copy per cell) and encoded there
-    (rcdms_amd.image.encode_png: literal-only deflate, see include/rcdm.h "PNG").  -> the file as `bytes`."""
+    (rcdms_amd.image.encode_png: literal-only deflate, see include/rcdm.h "PNG"; match=True: its match mode).  -> the file
+    as `bytes`."""
     from .image import encode_png
     cells = list(cells) if not isinstance(cells, torch.Tensor) else list(cells.unbind(0))
     if len(cells) != rows * cols or not cells:
@@ -94,7 +95,7 @@ def story_grid_png(cells, rows, cols):
     for i, c in enumerate(cells):
         r, k = divmod(i, cols)
         grid[r * h:(r + 1) * h, k * w:(k + 1) * w].copy_(c)
-    return encode_png(grid)[0]
+    return encode_png(grid, match=match)[0]
 
 
 def image_grid(imgs, rows, cols):

@@ -174,6 +174,8 @@ SYMBOLS = {
     "rcdm_png_bound": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_encode": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
+    "rcdm_png_match_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
+    "rcdm_png_encode_match": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -511,6 +513,15 @@ def png_workspace_bytes(desc):
 def png_encode(desc, src, workspace, dst, sizes, stream=None):
     _check(load().rcdm_png_encode(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
            "rcdm_png_encode")
+
+
+def png_match_workspace_bytes(desc):
+    return int(load().rcdm_png_match_workspace_bytes(C.byref(desc)))
+
+
+def png_encode_match(desc, src, workspace, dst, sizes, stream=None):
+    _check(load().rcdm_png_encode_match(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
+           "rcdm_png_encode_match")
 
 
 def assemble_input(lat, mask, masked, S, reps, frames, H, W, out, ld, c_pad, stream=None):

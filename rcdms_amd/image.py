@@ -377,17 +377,19 @@ def _png_device(device):
 
 class PngEncoder:
     """n images of h x w on one device: the descriptor's geometry, the workspace, the output streams (+ their sizes behind
-    them, so one download brings both) and a pinned host buffer of the same size, kept for every call of this shape."""
+    them, so one download brings both) and a pinned host buffer of the same size, kept for every call of this shape.
+    match=True: rcdm_png_encode_match (matches at the PNG row distances, per-block fallback to the literal form)."""
 
-    def __init__(self, h, w, n=1, device=None):
+    def __init__(self, h, w, n=1, device=None, match=False):
         self.device = _png_device(device)
-        self.h, self.w, self.n = int(h), int(w), int(n)
+        self.h, self.w, self.n, self.match = int(h), int(w), int(n), bool(match)
         d = self._desc(3 * self.w, 0, 0, hip.PNG_ADAPTIVE)
         self.bound = hip.png_bound(d)
         if self.bound == 0:
             raise hip.RcdmError(f"rcdm_png_encode takes 1..65535 images with sides 1..8192, got {self.n} of {self.h}x{self.w}")
         self.stride = (self.bound + 15) & ~15
-        self.workspace = torch.empty(hip.png_workspace_bytes(d), dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty((hip.png_match_workspace_bytes if self.match else hip.png_workspace_bytes)(d), dtype=torch.uint8,
+                                     device=self.device)
         self.out = torch.empty(self.n * self.stride + 8 * self.n, dtype=torch.uint8, device=self.device)
         self.host = torch.empty(self.out.shape, dtype=torch.uint8, pin_memory=True)
 
@@ -405,7 +407,7 @@ class PngEncoder:
         sizes_ptr = self.out.data_ptr() + self.n * self.stride if sizes is None else sizes
         d = self._desc(t.stride(1) if self.h > 1 else 3 * self.w, t.stride(0) if self.n > 1 else 0, stride if self.n > 1 else 0,
                        _png_filter(filter))
-        hip.png_encode(d, t.data_ptr(), self.workspace.data_ptr(), dst_ptr, sizes_ptr)
+        (hip.png_encode_match if self.match else hip.png_encode)(d, t.data_ptr(), self.workspace.data_ptr(), dst_ptr, sizes_ptr)
         return t
 
     def encode(self, frames, filter="adaptive"):
@@ -428,29 +430,30 @@ class PngEncoder:
 _PNG_ENCODERS = {}
 
 
-def png_encoder(h, w, n=1, device=None):
+def png_encoder(h, w, n=1, device=None, match=False):
     device = _png_device(device)
-    key = (int(h), int(w), int(n), device)
+    key = (int(h), int(w), int(n), device, bool(match))
     e = _PNG_ENCODERS.get(key)
     if e is None:
-        e = _PNG_ENCODERS[key] = PngEncoder(h, w, n, device)
+        e = _PNG_ENCODERS[key] = PngEncoder(h, w, n, device, match)
     return e
 
 
-def encode_png(frames, filter="adaptive"):
+def encode_png(frames, filter="adaptive", match=False):
     """Device uint8 frames (n, h, w, 3) or (h, w, 3), dense pixels with any row pitch / image stride -> list of PNG files as
     `bytes`.  Literal-only deflate (see include/rcdm.h, "PNG"): about Pillow's default size on noisy decoder output, far
-    larger than Pillow's on flat images.  filter: "adaptive" (per row) or one of none / sub / up / average / paeth."""
+    larger than Pillow's on flat images.  filter: "adaptive" (per row) or one of none / sub / up / average / paeth.
+    match=True: the match mode (rcdm_png_encode_match) — the same pixels, no block larger, flat frames several times smaller."""
     _png_filter(filter)
     t = _png_frames(frames)
-    return png_encoder(t.shape[1], t.shape[2], t.shape[0], t.device).encode(t, filter)
+    return png_encoder(t.shape[1], t.shape[2], t.shape[0], t.device, match).encode(t, filter)
 
 
-def save_png(paths, frames):
+def save_png(paths, frames, filter="adaptive", match=False):
     """Write frames[i] to paths[i] (a single path for a single (h, w, 3) frame)."""
     if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
         paths = [paths]
-    files = encode_png(frames)
+    files = encode_png(frames, filter, match)
     if len(files) != len(paths):
         raise ValueError(f"{len(paths)} paths for {len(files)} frames")
     for p, b in zip(paths, files):

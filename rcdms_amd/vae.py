@@ -158,10 +158,11 @@ class AutoencoderKLDecoder(nn.Module):
         return self._decode_program(z).forward_uint8(z)
 
     @torch.no_grad()
-    def decode_png(self, z, filter="adaptive"):
-        """z (n, 4, h, w) -> n PNG files as `bytes`: decode_uint8, then rcdm_png_encode on those frames (image.encode_png)."""
+    def decode_png(self, z, filter="adaptive", match=False):
+        """z (n, 4, h, w) -> n PNG files as `bytes`: decode_uint8, then rcdm_png_encode on those frames (image.encode_png);
+        match=True: rcdm_png_encode_match."""
         from .image import encode_png
-        return encode_png(self.decode_uint8(z), filter)
+        return encode_png(self.decode_uint8(z), filter, match)
 
 
 class DiagonalGaussianDistribution:

@@ -264,7 +264,7 @@ class RCDMsPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "tensor", return_dict: bool = True,
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: Optional[int] = 1,
-                 fix_context_order: bool = False, **kwargs):
+                 fix_context_order: bool = False, png_match: bool = False, **kwargs):
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -319,7 +319,7 @@ class RCDMsPipeline:
             if output_type == "png":                       # [[bytes] * f] * b: one PNG file per frame, encoded on the device
                 from rcdms_amd.image import encode_png
                 b, f = video.shape[:2]
-                files = encode_png(video.reshape(b * f, *video.shape[2:]))
+                files = encode_png(video.reshape(b * f, *video.shape[2:]), match=png_match)
                 video = [files[i * f:(i + 1) * f] for i in range(b)]
             return RCDMsPipelineOutput(videos=video) if return_dict else video
         video = self.decode_latents(final.to(text_embeddings.dtype))

@@ -4,12 +4,14 @@
   grid    the 2 x 5 comparison grid, 2560 x 1024, assembled from device cells -> one PNG file as `bytes`
 HIP: rcdm_png_encode (filter, block, assemble launches) + one download.  Host: PIL.Image.save of the same arrays (already
 on the host; the download the host path needs first is not counted) at Pillow's default (compress_level 6) and at 1.
+--match adds the match mode (rcdm_png_encode_match: encode_png(match=True), story_grid_png(match=True)) beside the literal-only
+one in the same process: its times, its launch-sequence device time and its file sizes, and the ratios match / literal-only.
 Frames are procedural cartoons (discs + gradient + Gaussian noise of --sigma grey levels): not decoder output.
 Times are a host clock around calls that end in a device synchronise, median [min, max] of `--repeats` windows of `--steps`
 calls after `--warmup` calls (tools/bench_image.py's convention); the device time of the three-launch sequence comes from
 device events, the split per kernel from `rocprofv3 --kernel-trace --stats -- python tools/bench_png.py --launch-only
 frames|grid` (recorded in profiles/png_encode.txt).  Also prints file sizes against Pillow's.  No pass / fail threshold.
-usage: python tools/bench_png.py [--steps 20] [--warmup 5] [--repeats 5] [--sigma 2.0] [--launch-only frames|grid]"""
+usage: python tools/bench_png.py [--steps 20] [--warmup 5] [--repeats 5] [--sigma 2.0] [--match] [--launch-only frames|grid]"""
 import argparse
 import io
 import json
@@ -58,6 +60,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sigma", type=float, default=2.0)
     ap.add_argument("--launch-only", choices=["frames", "grid"], help="only `--steps` launch sequences of one shape: the run to put under rocprofv3")
+    ap.add_argument("--match", action="store_true", help="also measure the match mode (with --launch-only: launch it instead)")
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -73,7 +76,8 @@ def main():
     d_grid = torch.from_numpy(grid).to(dev)
     sync = torch.cuda.synchronize
     if a.launch_only:
-        enc, src = (I.png_encoder(512, 512, 5, dev), d_frames) if a.launch_only == "frames" else (I.png_encoder(1024, 2560, 1, dev), d_grid)
+        enc, src = ((I.png_encoder(512, 512, 5, dev, a.match), d_frames) if a.launch_only == "frames" else
+                    (I.png_encoder(1024, 2560, 1, dev, a.match), d_grid))
         for _ in range(a.steps):
             enc.launch(src)
         sync()
@@ -93,6 +97,22 @@ def main():
 
     hip_frames = I.encode_png(d_frames)
     hip_grid = story_grid_png(cells, 2, 5)
+    match_frames = match_grid = None
+    if a.match:
+        res["frames_hip_match_ms"] = timed(lambda: I.encode_png(d_frames, match=True), *T)
+        res["grid_hip_match_ms"] = timed(lambda: story_grid_png(cells, 2, 5, match=True), *T)
+        res["story_hip_match_ms"] = round(res["frames_hip_match_ms"][0] + res["grid_hip_match_ms"][0], 3)
+        m5, m1 = I.png_encoder(512, 512, 5, dev, True), I.png_encoder(1024, 2560, 1, dev, True)
+        res["frames_hip_match_launches_ms"] = device_ms(lambda: m5.launch(d_frames), a.warmup, a.steps)
+        res["grid_hip_match_launches_ms"] = device_ms(lambda: m1.launch(d_grid), a.warmup, a.steps)
+        res["match_over_literal_launches"] = {"frames": round(res["frames_hip_match_launches_ms"] / res["frames_hip_launches_ms"], 3),
+                                              "grid": round(res["grid_hip_match_launches_ms"] / res["grid_hip_launches_ms"], 3)}
+        match_frames = I.encode_png(d_frames, match=True)
+        match_grid = story_grid_png(cells, 2, 5, match=True)
+        res["bytes_match"] = {"frames_hip_match": [len(f) for f in match_frames], "grid_hip_match": len(match_grid),
+                              "frames_hip": [len(f) for f in hip_frames], "grid_hip": len(hip_grid)}
+        res["size_ratio_match_vs_literal"] = {"frames": round(sum(map(len, match_frames)) / sum(map(len, hip_frames)), 3),
+                                              "grid": round(len(match_grid) / len(hip_grid), 3)}
     try:
         from PIL import Image
     except ImportError:
@@ -119,6 +139,12 @@ def main():
         for f, want in zip(hip_frames, frames):
             assert np.array_equal(np.asarray(Image.open(io.BytesIO(f))), want)
         assert np.array_equal(np.asarray(Image.open(io.BytesIO(hip_grid))), grid)
+        if a.match:
+            res["size_ratio_match_vs_pillow_default"] = {"frames": round(sum(map(len, match_frames)) / sum(b["frames_pillow_default"]), 3),
+                                                         "grid": round(len(match_grid) / b["grid_pillow_default"], 3)}
+            for f, want in zip(match_frames, frames):
+                assert np.array_equal(np.asarray(Image.open(io.BytesIO(f))), want)
+            assert np.array_equal(np.asarray(Image.open(io.BytesIO(match_grid))), grid)
         res["files_decode_to_input"] = True
         import PIL
         res["pillow"] = PIL.__version__
