@@ -8,6 +8,7 @@ with procedural name-seeded weights (rcdms_amd/synth.py).  Run in the build cont
     python -m oracle.make_golden --only skewed                 # full-width UNet with the second ("skewed") weight family, 32x32
     python -m oracle.make_golden --only rank1ctx               # context rows 2..9 with L identical rows each, tiny + full width
     python -m oracle.make_golden --only sdlike                 # full-width UNet with the third ("sdlike") weight family, 32x32
+    python -m oracle.make_golden --only probe                  # two-level 320 / 640 probe UNet (tests/test_hip_planforms.py), five small geometries
 
 What is stored: small inputs and the reference outputs (fp32 .npz), plus a digest of the reference's
 state-dict key/shape list so the mirrored classes are checked to have the identical 1286-key layout.
@@ -132,6 +133,74 @@ def full_unet():
         y = m(x, torch.tensor(t), encoder_hidden_states=s["ctx"], return_dict=False)[0]
         print("  reference forward %dx%d: %.1f s" % (hw, hw, time.time() - t0))
         save(f"unet_full_{hw}", t=np.int64(t), y=y, digest=dig)
+
+
+PROBE_SEED = 11
+# name: (b, f, H, W, timestep, input seed, motion_module_resolutions) — the geometries of tests/test_hip_planforms.py
+PROBE_CASES = {
+    "a": (2, 5, 16, 16, 981, 70, None),
+    "b": (1, 3, 16, 24, 441, 72, None),
+    "c": (1, 2, 32, 32, 741, 74, None),
+    "d": (2, 5, 8, 16, 21, 76, None),
+    "mm12": (1, 3, 16, 24, 601, 78, (1, 2)),   # motion modules in the down blocks only (reference unet.py:199: 2 ** (3 - i))
+    # the smallest geometry whose 640-channel upsampler (2560 source pixels) takes the four-phase form; inputs are NOT stored:
+    # the seed-80 synthetic story, assembled as the CFG step does (the full-width fixtures' convention)
+    "e": (2, 5, 32, 32, 301, 80, None),
+}
+PROBE_L, PROBE_CTX_DIM = 13, 64
+
+
+def build_reference_probe(resolutions=None):
+    """The reference UNet3DConditionModel at two levels of the REAL widths (320 with head dim 40, 640 with head dim 80), one
+    layer per block, cross-attention in every block: 136.3 M parameters, 466 keys."""
+    ref_unet = ref_scaffold.load_reference_models()
+    cfg = dict(ref_scaffold.SD15_UNET_CONFIG)
+    cfg.update(in_channels=9, block_out_channels=[320, 640], layers_per_block=1, cross_attention_dim=PROBE_CTX_DIM,
+               down_block_types=["CrossAttnDownBlock3D"] * 2, up_block_types=["CrossAttnUpBlock3D"] * 2)
+    kw = dict(ref_scaffold.TESTING_YAML_UNET_KWARGS)
+    if resolutions is not None:
+        kw["motion_module_resolutions"] = list(resolutions)
+    return ref_unet.UNet3DConditionModel.from_config(cfg, **kw).eval()
+
+
+@torch.no_grad()
+def probe_unet():
+    """unet_probe_<name>.npz: inputs from seeds as tiny_unet() draws them (stored), the reference's fp32 output.  Geometry "a" holds ONE
+    sample twice (the latents the CFG step duplicates, RCDMs_pipeline.py:481) with different context rows, so the same file
+    serves the shared-prefix plan."""
+    models = {}
+    for name, (b, f, H, W, t, seed, res) in PROBE_CASES.items():
+        if res not in models:
+            m = build_reference_probe(res)
+            models[res] = (m, load_procedural(m, seed=PROBE_SEED))
+            print("  probe UNet (motion_module_resolutions %s): %.1f M parameters, %d keys"
+                  % (res, sum(p.numel() for p in m.parameters()) / 1e6, len(m.state_dict())))
+        m, dig = models[res]
+        if name == "e":
+            st = synth.synthetic_story(stories=1, latent_hw=(H, W), ctx_len=PROBE_L, ctx_dim=PROBE_CTX_DIM, seed=seed)
+            x, ctx = torch.cat([torch.cat([st["latents"]] * 2), st["mask"], st["masked_latents"]], dim=1), st["ctx"]
+            assert tuple(x.shape) == (b, 9, f, H, W) and tuple(ctx.shape) == (b * f, PROBE_L, PROBE_CTX_DIM)
+        else:
+            x = randn((1, 9, f, H, W), seed).repeat(2, 1, 1, 1, 1) if name == "a" else randn((b, 9, f, H, W), seed)
+            ctx = randn((b * f, PROBE_L, PROBE_CTX_DIM), seed + 1)
+        t0 = time.time()
+        y = m(x, torch.tensor(t), encoder_hidden_states=ctx, return_dict=False)[0]
+        assert torch.isfinite(y).all()
+        print("  reference forward %s (b=%d f=%d %dx%d): %.1f s; |y| rms %.3f max %.3f"
+              % (name, b, f, H, W, time.time() - t0, y.pow(2).mean().sqrt(), y.abs().max()))
+        if name == "e":
+            save(f"unet_probe_{name}", t=np.int64(t), y=y, digest=dig, story_seed=np.int64(seed))
+        else:
+            save(f"unet_probe_{name}", x=x, ctx=ctx, t=np.int64(t), y=y, digest=dig)
+    # one ResnetBlock3D at a Winograd shape (640 -> 640, one 8x8 image) on LOW-VARIANCE rows (x ~ 0.03 N: variance 9e-4): a GroupNorm
+    # is scale-invariant but for its eps, so here — unlike on the unit-variance activations of the UNet fixtures, where an eps of 1e-3
+    # moves the output by less than the f16 path's own error — the eps that reaches the Winograd input transform is visible
+    import refsrc.models.resnet as r_res
+    m = r_res.ResnetBlock3D(in_channels=640, out_channels=640, temb_channels=1280, eps=1e-5, groups=32, non_linearity="silu",
+                            use_inflated_groupnorm=False).eval()
+    dig = load_procedural(m, seed=PROBE_SEED + 1)
+    x, temb = 0.03 * randn((1, 640, 1, 8, 8), 82), randn((1, 1280), 83)
+    save("unet_probe_resnet_lowvar", x=x, temb=temb, y=m(x, temb), digest=dig)
 
 
 ALT_SEED, ALT_STORY_SEED, ALT_T = 5, 43, 501
@@ -379,6 +448,8 @@ if __name__ == "__main__":
         print("prior transformer"); prior(["prior_tiny"] + (["prior_full"] if a.full else []))
     if a.full or a.only == "full":
         print("full UNet"); full_unet()
+    if a.only == "probe":
+        print("probe UNet (320 / 640)"); probe_unet()
     if a.only == "rank1ctx":
         print("rank-1 context rows"); rank1_context()
     if a.only == "sdlike":

@@ -27,16 +27,25 @@ def emit_resnet(plan, w, x, geo, temb, out, eps=1e-5, groups=32, out_scale=1.0, 
     # ---- norm1 + conv1.  Winograd form (wino_level): the norm is a statistics-only launch, its apply + SiLU rides in the input
     # transform; its output transform leaves norm2's per-tile statistics when conv2 takes that form too
     res = x
+
+    def unfolded_shortcut():
+        """conv_shortcut(x) as its own 1x1 GEMM (SC_FOLD off, or a width the fold does not take) — whichever form conv1 takes:
+        a nine-tap conv2 behind a Winograd conv1 (sides below WINO_SHORTCUT_MIN_SIDE) reads it as its residual too."""
+        if u2 or w.shortcut is None:
+            return x
+        sc = plan.rows("res_sc", g.M, w.cout)
+        emit_gemm(plan, x, w.shortcut, w.cout, w.cin, sc, bias=w.sb)
+        return sc
+
     if u1:
         gn1 = emit_groupnorm_stats(plan, x, g.b, g.f * g.hw, w.g1, w.b1, eps, groups)   # (first: x may carry a producer's statistics)
+        res = unfolded_shortcut()
         emit_conv3x3_wino(plan, x, g.n_img, g.H, g.W, w.wino1, w.cin, w.cout, h1, bias=w.cb1, rowvec=rv, gn=gn1,
                           gn_out=cross if u2 else None)
     else:
         a1 = plan.rows("norm", g.M, x.C)
         emit_groupnorm(plan, x, g.b, g.f * g.hw, w.g1, w.b1, eps, True, a1, groups)   # (first: x may carry a producer's statistics)
-        if not u2 and w.shortcut is not None:
-            res = plan.rows("res_sc", g.M, w.cout)
-            emit_gemm(plan, x, w.shortcut, w.cout, w.cin, res, bias=w.sb)
+        res = unfolded_shortcut()
         emit_conv3x3(plan, a1, g.n_img, g.H, g.W, w.conv1, w.cin, w.cout, h1, bias=w.cb1, rowvec=rv, gn=cross)
     # ---- norm2 + conv2 (+ conv_shortcut(x) | + x)
     if u2:

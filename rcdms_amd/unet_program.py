@@ -185,6 +185,10 @@ class UNetProgram:
             next_resnet: final_out is, as it stands, the input of another ResNet block of this geometry (down path: the next
             layer of the block) — its norm1 is then the op emitted right after this layer's last one."""
             stages = ["r"] + (["t"] if kind_attn else []) + (["m"] if has_motion(res) else [])
+            if ("m" in stages) != (pb + f"motion_modules.{j}.temporal_transformer.norm.weight" in sd):
+                raise hip.RcdmError(f"{pb}motion_modules.{j}: the state dict {'lacks' if 'm' in stages else 'holds'} a motion module "
+                                    f"that motion_module_resolutions {tuple(cfg['motion_module_resolutions'])} "
+                                    f"{'places' if 'm' in stages else 'does not place'} at resolution {res}")
             cur = x
             cout = sd[pb + f"resnets.{j}.conv1.weight"].shape[0]
             for si, st in enumerate(stages):
@@ -266,7 +270,9 @@ class UNetProgram:
                     dst = final
                 else:
                     dst = plan.rows("up_tmp", geo.M, rev[i])
-                cur = layer(pb, j, kind == "CrossAttnUpBlock3D", 2 ** (nlev - 1 - i), x, geo, dst)
+                # (up block i owns motion modules by 2 ** (3 - i) whatever the number of levels: unet.py:199 — the rule the
+                #  model classes build their state dict by, which agrees with the level's own 2 ** lvl at four levels only)
+                cur = layer(pb, j, kind == "CrossAttnUpBlock3D", 2 ** (3 - i), x, geo, dst)
                 k -= 1
             if not last_block:
                 emit_upsample_conv(plan, pk, pb + "upsamplers.0.conv.weight", cur, geo.n_img, geo.H, geo.W, rev[i], h_view(k),

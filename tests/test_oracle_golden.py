@@ -55,6 +55,9 @@ def mirrored(kind):
         if kind == "resnet_64_64":
             return resnet.ResnetBlock3D(in_channels=64, out_channels=64, temb_channels=256, eps=1e-5, groups=32,
                                         non_linearity="silu", use_inflated_groupnorm=False)
+        if kind == "resnet_640_lowvar":
+            return resnet.ResnetBlock3D(in_channels=640, out_channels=640, temb_channels=1280, eps=1e-5, groups=32,
+                                        non_linearity="silu", use_inflated_groupnorm=False)
         if kind == "transformer_64":
             return attention.Transformer3DModel(8, 8, in_channels=64, num_layers=1, cross_attention_dim=64,
                                                 norm_num_groups=32, unet_use_cross_frame_attention=False,
@@ -72,11 +75,19 @@ def mirrored(kind):
                                              block_out_channels=(64, 128, 256, 256), **UNET_KW)
         if kind == "unet_full":
             return unet.UNet3DConditionModel(in_channels=9, cross_attention_dim=768, **UNET_KW)
+        if kind in ("unet_probe", "unet_probe_mm12"):
+            # two levels at the REAL widths (320: head dim 40, 640: head dim 80), one layer per block; _mm12: motion modules
+            # at resolutions (1, 2) only, which the reference places in the down blocks alone (unet.py:199)
+            kw = dict(UNET_KW, motion_module_resolutions=[1, 2]) if kind.endswith("mm12") else UNET_KW
+            return unet.UNet3DConditionModel(in_channels=9, cross_attention_dim=64, block_out_channels=(320, 640),
+                                             layers_per_block=1, down_block_types=("CrossAttnDownBlock3D",) * 2,
+                                             up_block_types=("CrossAttnUpBlock3D",) * 2, **kw)
     raise KeyError(kind)
 
 
 SEEDS = {"resnet_64_128": 1, "resnet_64_64": 1, "transformer_64": 2, "motion_64": 3, "downsample_64": 4,
-         "upsample_64": 5, "conv_in_9_64": 6, "unet_tiny": 7, "unet_full": 0}
+         "upsample_64": 5, "conv_in_9_64": 6, "unet_tiny": 7, "unet_full": 0,
+         "unet_probe": 11, "unet_probe_mm12": 11, "resnet_640_lowvar": 12}
 
 
 def weights(kind):
@@ -116,6 +127,44 @@ def test_unet_layout_matches_reference_1286_keys():
         assert digest(sd) == gold("unet_full_32")["digest"]
     t = mirrored("unet_tiny")
     assert digest(t.state_dict()) == gold("unet_tiny_16")["digest"]
+
+
+def probe_config(resolutions=(1, 2, 4, 8)):
+    """The oracle's config dict of the two-level probe UNet (mirrored("unet_probe"))."""
+    cfg = dict(O.SD15_STAGE2_CONFIG)
+    cfg.update(block_out_channels=(320, 640), layers_per_block=1, cross_attention_dim=64,
+               down_block_types=("CrossAttnDownBlock3D",) * 2, up_block_types=("CrossAttnUpBlock3D",) * 2,
+               motion_module_resolutions=tuple(resolutions))
+    return cfg
+
+
+def test_probe_unet_layout_matches_reference_466_keys():
+    """The two-level 320 / 640 probe of tests/test_hip_planforms.py: 466 keys, the reference's key / shape digest; with
+    motion_module_resolutions (1, 2) the reference keeps the motion modules of the down blocks only (346 keys)."""
+    sd = mirrored("unet_probe").state_dict()
+    assert len(sd) == 466
+    for name in ("a", "b", "c", "d", "e"):
+        assert digest(sd) == gold(f"unet_probe_{name}")["digest"]
+    sd12 = mirrored("unet_probe_mm12").state_dict()
+    assert len(sd12) == 346
+    assert digest(sd12) == gold("unet_probe_mm12")["digest"]
+    assert any(k.startswith("down_blocks.1.motion_modules.") for k in sd12)
+    assert not any(k.startswith("up_blocks.") and ".motion_modules." in k for k in sd12)
+    g = gold("unet_probe_resnet_lowvar")
+    assert digest(mirrored("resnet_640_lowvar").state_dict()) == g["digest"]
+    assert_close(O.resnet_block(weights("resnet_640_lowvar"), "", g["x"], g["temb"], 32, 1e-5), g["y"])
+    assert 8e-4 < g["x"].var().item() < 1e-3      # GroupNorm input variance ~ 9e-4: eps 1e-5 is 1 % of it, 1e-3 would double it
+
+
+@pytest.mark.parametrize("name", ["b", "mm12"])
+def test_probe_unet_oracle(name):
+    """The oracle restatement at the real widths (head dims 40 and 80), a non-square latent, 3 of the 5 positional rows."""
+    g = gold(f"unet_probe_{name}")
+    kind = "unet_probe_mm12" if name == "mm12" else "unet_probe"
+    cfg = probe_config((1, 2)) if name == "mm12" else probe_config()
+    with torch.no_grad():
+        y = O.unet_forward(weights(kind), cfg, g["x"], torch.tensor(g["t"]), g["ctx"])
+    assert_close(y, g["y"])
 
 
 @pytest.mark.parametrize("name", ["unet_tiny_16", "unet_tiny_32", "unet_tiny_16_tvec"])
