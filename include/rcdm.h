@@ -786,6 +786,69 @@ size_t rcdm_png_match_workspace_bytes(const rcdm_png_desc* d);
 int rcdm_png_encode_match(const rcdm_png_desc* d, const void* src, void* workspace, void* dst, uint64_t* sizes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG, reading: n PNG files, uploaded as ONE byte buffer, -> n uint8 HWC images (RGB or BGR) in device memory.  What the
+ * drivers do on the host with cv2.imdecode over the whole test set (stage2_batchtest_rcdms_model.py:41-46, :446-450) and
+ * with Image.open(...).convert("RGB") (:256-260, :304-343).  Files of one call may differ in size and kind, so the call
+ * takes one record per file.  The HOST walks the container (signature, chunk headers — rcdms_amd/image.py) and fills the
+ * records and the IDAT table; the DEVICE does everything that touches the bulk: gathering the IDAT payloads, zlib header,
+ * inflate (stored, fixed and dynamic blocks, window 32 K), Adler-32, the five PNG filters, the colour conversion.
+ *   scope       bit depth 8, no interlace; colour types 0 grey (replicated), 2 RGB, 3 palette (looked up; an index beyond
+ *               plte_entries is black), 4 grey + alpha and 6 RGBA (alpha dropped).  Ancillary chunks are the host's to skip.
+ *   kernels     two launches on `stream`, no host readback, graph-capturable.  One wavefront per file in both: inflate
+ *               (symbol decode is wave-uniform, a match of length L is copied by L lanes in an LDS ring of the last 32 K),
+ *               then unfilter + convert (a lane per row of a 64-row band, each row one pixel behind the row above).
+ *   status[i]   0, or the first thing wrong with file i (RCDM_PNG_E* below).  A bad FILE is never a bad CALL: the call
+ *               returns 0, the other files come out right, and no byte of a bad file's image is written.
+ *   workspace   file i uses RCDM_PNG_FILE_WORKSPACE(zlib_bytes, h * (1 + bpp * w)) bytes at workspace + ws_offset (a
+ *               multiple of 16, regions disjoint — the host lays them end to end): its zlib stream, then its inflated
+ *               rows.  Read and written, 16-byte aligned; src is only read.
+ *   rcdm_png_decode_workspace_bytes  the largest ws_offset + size over the records: what `workspace` must hold.  It is
+ *                                    also the only check of the records: 0 for a side outside 1..8192, a colour type
+ *                                    not listed, dst_pitch < 3 w, a ws_offset that is no multiple of 16, or n outside
+ *                                    1..65535.  rcdm_png_decode itself takes device pointers and cannot look.
+ * The records and the IDAT table are the caller's contract, trusted as the host's own work (offsets inside the buffers it
+ * uploaded, rows that do not overlap, aligned regions): the kernels do not re-check them, but for a side or colour type
+ * out of range, for which nothing can be inflated and status[i] is RCDM_PNG_EUNDERRUN.  Everything
+ * that comes out of a FILE's bytes — lengths, distances, code lengths, stored sizes, filter bytes — is checked before a
+ * position is formed from it.
+ * RCDM_EINVAL: null pointers, n < 1, n_idat < 1, an order other than RCDM_PNG_RGB / RCDM_PNG_BGR, workspace not 16-byte
+ * aligned, status not 4-byte aligned, files / idats not 8-byte aligned.  RCDM_ESHAPE: n > 65535.  All before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_PNG_RGB 0
+#define RCDM_PNG_BGR 1
+#define RCDM_PNG_EZLIB 1      /* zlib header: CM != 8, window > 32 K, preset dictionary, header checksum */
+#define RCDM_PNG_ETRUNC 2     /* the stream ends inside a block or in front of its Adler-32 */
+#define RCDM_PNG_EBLOCK 3     /* block type 3 */
+#define RCDM_PNG_ESTORED 4    /* stored block: LEN != ~NLEN */
+#define RCDM_PNG_ECODES 5     /* code lengths: over-subscribed, incomplete (but for ONE distance code), too many, no end-of-block */
+#define RCDM_PNG_ESYMBOL 6    /* length symbol 286 / 287, distance symbol 30 / 31, or bits that no code owns */
+#define RCDM_PNG_EDISTANCE 7  /* a distance that reaches in front of the first output byte */
+#define RCDM_PNG_EOVERRUN 8   /* the stream inflates to more than h * (1 + bpp * w) bytes */
+#define RCDM_PNG_EUNDERRUN 9  /* ... to fewer */
+#define RCDM_PNG_EADLER 10    /* Adler-32 of the inflated bytes */
+#define RCDM_PNG_EFILTER 11   /* a filter byte above 4 */
+#define RCDM_PNG_FILE_WORKSPACE(zlib_bytes, raw_bytes) ((((zlib_bytes) + 15) & ~(uint64_t)15) + (((raw_bytes) + 15) & ~(uint64_t)15))
+typedef struct {                   /* one per file, filled by the host from the container */
+  uint64_t src_offset, src_bytes;  /* the file inside the uploaded byte buffer */
+  uint64_t dst_offset;             /* first output byte of this image */
+  uint64_t ws_offset;              /* this file's region of the workspace */
+  uint64_t zlib_bytes;             /* sum of its IDAT payloads */
+  uint32_t dst_pitch;              /* bytes between output rows, >= 3 w */
+  uint32_t w, h;                   /* 1..8192 each */
+  uint32_t color_type;             /* 0, 2, 3, 4, 6 */
+  uint32_t idat_first, idat_count; /* this file's run in the IDAT table */
+  uint32_t plte_offset;            /* colour type 3: the PLTE payload, relative to src_offset */
+  uint32_t plte_entries;           /* its length / 3, <= 256 */
+} rcdm_png_file;
+typedef struct {
+  uint64_t offset;                 /* payload of one IDAT chunk, relative to the file's src_offset */
+  uint32_t bytes, reserved;
+} rcdm_png_idat;
+size_t rcdm_png_decode_workspace_bytes(const rcdm_png_file* files, int n);
+int rcdm_png_decode(const rcdm_png_file* files, const rcdm_png_idat* idats, int n, int n_idat, int order, const void* src,
+                    void* workspace, void* dst, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

@@ -99,7 +99,22 @@ class PngDesc(C.Structure):
                 ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32)]
 
 
+class PngFile(C.Structure):
+    _fields_ = [("src_offset", C.c_uint64), ("src_bytes", C.c_uint64), ("dst_offset", C.c_uint64), ("ws_offset", C.c_uint64),
+                ("zlib_bytes", C.c_uint64), ("dst_pitch", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("color_type", C.c_uint32), ("idat_first", C.c_uint32), ("idat_count", C.c_uint32), ("plte_offset", C.c_uint32),
+                ("plte_entries", C.c_uint32)]
+
+
+class PngIdat(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
+PNG_RGB, PNG_BGR = 0, 1
+PNG_STATUS = {1: "RCDM_PNG_EZLIB", 2: "RCDM_PNG_ETRUNC", 3: "RCDM_PNG_EBLOCK", 4: "RCDM_PNG_ESTORED", 5: "RCDM_PNG_ECODES",
+              6: "RCDM_PNG_ESYMBOL", 7: "RCDM_PNG_EDISTANCE", 8: "RCDM_PNG_EOVERRUN", 9: "RCDM_PNG_EUNDERRUN",
+              10: "RCDM_PNG_EADLER", 11: "RCDM_PNG_EFILTER"}
 IMAGE_TILE = 32                                         # RCDM_IMAGE_TILE
 IMAGE_U8, IMAGE_F32_NCHW, IMAGE_F16_ROWS = 0, 1, 2      # ResampleDesc.mode
 FRAMES_F16_ROWS, FRAMES_F32_NCHW = 0, 1                 # FramesU8Desc.src_kind
@@ -176,6 +191,8 @@ SYMBOLS = {
     "rcdm_png_encode": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
     "rcdm_png_match_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_encode_match": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
+    "rcdm_png_decode_workspace_bytes": (_SZ, [_P, C.c_int]),
+    "rcdm_png_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -513,6 +530,22 @@ def png_workspace_bytes(desc):
 def png_encode(desc, src, workspace, dst, sizes, stream=None):
     _check(load().rcdm_png_encode(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
            "rcdm_png_encode")
+
+
+def png_file_workspace(zlib_bytes, raw_bytes):
+    """RCDM_PNG_FILE_WORKSPACE: the bytes of one file's workspace region."""
+    return ((zlib_bytes + 15) & ~15) + ((raw_bytes + 15) & ~15)
+
+
+def png_decode_workspace_bytes(files, n):
+    """files: a host (PngFile * n) array."""
+    return int(load().rcdm_png_decode_workspace_bytes(C.addressof(files), n))
+
+
+def png_decode(files, idats, n, n_idat, order, src, workspace, dst, status, stream=None):
+    """files / idats / status: device pointers."""
+    _check(load().rcdm_png_decode(files, idats, n, n_idat, order, src, workspace, dst, status,
+                                  stream_ptr() if stream is None else stream), "rcdm_png_decode")
 
 
 def png_match_workspace_bytes(desc):

@@ -13,10 +13,17 @@ Back end — RCDMs_pipeline.py:274-287 and the driver's tensor2list: `frames_to_
 truncated, from the VAE decoder's f16 rows or an fp32 NCHW tensor straight to uint8 HWC (rcdm_frames_to_u8).
 Files — the driver's PIL.Image.save calls (:378-401): `encode_png` / `save_png` / `PngEncoder` turn device uint8 frames into
 complete PNG files on the device (rcdm_png_encode: adaptive filters, literal-only Huffman deflate), one download per call.
+Files, reading — the drivers' cv2.imdecode over the test set (:41-46, :446-450) and Image.open(...).convert("RGB") (:256-260,
+:304-343): `decode_png` / `load_png` / `PngDecoder` walk the container on the host (chunk headers only), upload the files as
+one byte buffer and leave the frames on the device as uint8 HWC, RGB or — cv2's order, which the drivers hand on unflipped —
+BGR (rcdm_png_decode: inflate, Adler-32, the five filters and the colour conversion on the device, one wavefront per file).
 
 No CPU path: a call without a GPU raises (only `resample_tables` and the geometry helpers are host code)."""
+import ctypes
 import math
+import struct
 import types
+import zlib
 
 import numpy as np
 import torch
@@ -459,3 +466,194 @@ def save_png(paths, frames, filter="adaptive", match=False):
     for p, b in zip(paths, files):
         with open(p, "wb") as f:
             f.write(b)
+
+
+# ------------------------------------------------------------------------------------------------
+# PNG files -> uint8 frames on the device (rcdm_png_decode): the container is walked here, the bulk is the device's
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_ORDERS = {"rgb": hip.PNG_RGB, "bgr": hip.PNG_BGR}
+_PNG_BPP = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_PNG_MAX_SIDE = 8192
+
+
+def png_walk(data, index=0, check_crc=False):
+    """The chunk headers of one file (8 bytes per chunk; the payloads are not touched unless check_crc) ->
+    SimpleNamespace(w, h, color_type, idats [(payload offset, bytes)], plte (offset, entries)).  Ancillary chunks are
+    skipped, tRNS included (what Image.convert("RGB") and cv2.IMREAD_COLOR make of them).  NotImplementedError, naming the
+    file index, for what rcdm_png_decode does not read: a bit depth other than 8, Adam7, a side above 8192, a missing IHDR /
+    IDAT / PLTE; ValueError for what is not a PNG container at all (signature, a chunk that runs past the end, a CRC)."""
+    data = memoryview(data)
+    if len(data) < 8 or bytes(data[:8]) != PNG_SIGNATURE:
+        raise ValueError(f"file {index}: not a PNG signature")
+    out = types.SimpleNamespace(w=None, h=None, color_type=None, idats=[], plte=None)
+    off = 8
+    while off + 12 <= len(data):
+        n, = struct.unpack(">I", data[off:off + 4])
+        kind = bytes(data[off + 4:off + 8])
+        if off + 12 + n > len(data):
+            raise ValueError(f"file {index}: a {kind!r} chunk of {n} bytes runs past the end of the file")
+        if check_crc:
+            stored, = struct.unpack(">I", data[off + 8 + n:off + 12 + n])
+            if stored != zlib.crc32(data[off + 4:off + 8 + n]) & 0xFFFFFFFF:
+                raise ValueError(f"file {index}: CRC of the {kind!r} chunk at byte {off}")
+        if kind == b"IHDR":
+            if n != 13:
+                raise ValueError(f"file {index}: an IHDR of {n} bytes")
+            w, h, depth, ct, comp, filt, interlace = struct.unpack(">IIBBBBB", data[off + 8:off + 21])
+            if depth != 8 or ct not in _PNG_BPP:
+                raise NotImplementedError(f"file {index}: bit depth {depth}, colour type {ct}: rcdm_png_decode reads 8-bit grey, "
+                                          "RGB, palette, grey + alpha and RGBA")
+            if interlace:
+                raise NotImplementedError(f"file {index}: Adam7 interlacing is not read")
+            if comp or filt:
+                raise NotImplementedError(f"file {index}: compression method {comp}, filter method {filt}")
+            if not (1 <= w <= _PNG_MAX_SIDE and 1 <= h <= _PNG_MAX_SIDE):
+                raise NotImplementedError(f"file {index}: {h}x{w}: sides are 1..{_PNG_MAX_SIDE}")
+            out.w, out.h, out.color_type = w, h, ct
+        elif kind == b"PLTE":
+            out.plte = (off + 8, min(n // 3, 256))
+        elif kind == b"IDAT":
+            out.idats.append((off + 8, n))
+        elif kind == b"IEND":                            # a missing IEND is let pass, as Pillow and cv2 do
+            break
+        off += 12 + n
+    if out.w is None:
+        raise NotImplementedError(f"file {index}: no IHDR chunk")
+    if not out.idats or sum(n for _, n in out.idats) == 0:
+        raise NotImplementedError(f"file {index}: no IDAT data")
+    if out.color_type == 3 and out.plte is None:
+        raise NotImplementedError(f"file {index}: colour type 3 without a PLTE chunk")
+    return out
+
+
+def _png_files(files):
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    files = list(files)
+    if not files or not all(isinstance(f, (bytes, bytearray, memoryview)) for f in files):
+        raise TypeError("PNG files are one bytes object or a non-empty sequence of them")
+    if len(files) > 65535:
+        raise ValueError(f"rcdm_png_decode takes 1..65535 files per call, got {len(files)}")
+    return files
+
+
+def png_decode_plan(files, check_crc=False, pitch=None, gap=0):
+    """Host side of one rcdm_png_decode call: walks every file and lays out the buffers ->
+    SimpleNamespace(n, n_idat, records (hip.PngFile * n), idats (hip.PngIdat * n_idat), src uint8 numpy (the files, each at
+    a 16-byte boundary), dst_bytes, workspace_bytes, shapes [(h, w)]).  pitch(w) -> bytes between output rows (default
+    dense, 3 w); gap: bytes left free in front of every image (both for tests that guard the output)."""
+    files = _png_files(files)
+    walks = [png_walk(f, i, check_crc) for i, f in enumerate(files)]
+    n, n_idat = len(files), sum(len(wk.idats) for wk in walks)
+    records, idats = (hip.PngFile * n)(), (hip.PngIdat * n_idat)()
+    src_at, dst_at, ws_at, idat_at = 0, 0, 0, 0
+    for i, (f, wk) in enumerate(zip(files, walks)):
+        r = records[i]
+        r.src_offset, r.src_bytes = src_at, len(f)
+        src_at += (len(f) + 15) & ~15
+        r.w, r.h, r.color_type = wk.w, wk.h, wk.color_type
+        r.dst_pitch = 3 * wk.w if pitch is None else int(pitch(wk.w))
+        dst_at += gap
+        r.dst_offset = dst_at
+        dst_at += r.dst_pitch * wk.h
+        r.idat_first, r.idat_count = idat_at, len(wk.idats)
+        for off, nb in wk.idats:
+            idats[idat_at].offset, idats[idat_at].bytes = off, nb
+            idat_at += 1
+        r.zlib_bytes = sum(nb for _, nb in wk.idats)
+        r.ws_offset = ws_at
+        ws_at += hip.png_file_workspace(r.zlib_bytes, wk.h * (1 + _PNG_BPP[wk.color_type] * wk.w))
+        r.plte_offset, r.plte_entries = wk.plte if wk.plte is not None and wk.color_type == 3 else (0, 0)
+    src = np.zeros(src_at, dtype=np.uint8)
+    for r, f in zip(records, files):
+        src[r.src_offset:r.src_offset + len(f)] = np.frombuffer(f, dtype=np.uint8)
+    return types.SimpleNamespace(n=n, n_idat=n_idat, records=records, idats=idats, src=src, dst_bytes=dst_at + gap, workspace_bytes=ws_at,
+                                 shapes=[(wk.h, wk.w) for wk in walks])
+
+
+class PngDecoder:
+    """rcdm_png_decode on one device: `decode(files)` is one upload of the file bytes, one of the tables, one launch
+    sequence (inflate, unfilter + convert; `launch` alone is graph-capturable) and one download of n status words."""
+
+    def __init__(self, device=None):
+        self.device = _png_device(device)
+        if self.device.type != "cuda":
+            raise hip.RcdmError("decode_png runs on the HIP path only: there is no CPU decoder here")
+
+    def upload(self, plan):
+        """-> (src, tables) on the device; tables: the records, then the IDAT table (both 8-byte aligned)."""
+        rec = np.frombuffer(bytes(plan.records), dtype=np.uint8)
+        tab = np.concatenate([rec, np.frombuffer(bytes(plan.idats), dtype=np.uint8)])
+        assert ctypes.sizeof(hip.PngFile) % 8 == 0
+        return torch.from_numpy(plan.src).to(self.device), torch.from_numpy(tab).to(self.device)
+
+    def launch(self, plan, src, tables, workspace, dst, status, order="rgb"):
+        """The two launches on the current stream.  workspace / dst: device uint8 tensors of at least plan.workspace_bytes /
+        plan.dst_bytes; status: device int32 [n]."""
+        if order not in PNG_ORDERS:
+            raise ValueError(f"order {order!r}: rgb or bgr")
+        if workspace.numel() < plan.workspace_bytes or dst.numel() < plan.dst_bytes or status.numel() < plan.n:
+            raise ValueError("workspace, dst or status is smaller than the plan asks for")
+        hip.png_decode(tables.data_ptr(), tables.data_ptr() + plan.n * ctypes.sizeof(hip.PngFile), plan.n, plan.n_idat, PNG_ORDERS[order],
+                       src.data_ptr(), workspace.data_ptr(), dst.data_ptr(), status.data_ptr())
+
+    def decode(self, files, order="rgb", check_crc=False):
+        """-> list of n device uint8 (h, w, 3) tensors: views of ONE buffer with dense rows, in order (`PngDecoder.batch` views
+        a run of equal sizes as (n, h, w, 3) without a copy)."""
+        plan = png_decode_plan(files, check_crc)
+        if hip.png_decode_workspace_bytes(plan.records, plan.n) != plan.workspace_bytes:
+            raise hip.RcdmError("rcdm_png_decode_workspace_bytes disagrees with the host's layout")
+        src, tables = self.upload(plan)
+        workspace = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=self.device)
+        dst = torch.empty(plan.dst_bytes, dtype=torch.uint8, device=self.device)
+        status = torch.empty(plan.n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.launch(plan, src, tables, workspace, dst, status, order)
+        bad = status.cpu().numpy()                        # the one download; it also orders the buffers' release
+        for i in np.flatnonzero(bad):
+            raise hip.RcdmError(f"rcdm_png_decode: file {int(i)}: {hip.PNG_STATUS.get(int(bad[i]), int(bad[i]))}")
+        out, at = [], 0
+        for h, w in plan.shapes:
+            out.append(dst[at:at + h * w * 3].view(h, w, 3))
+            at += h * w * 3
+        return out
+
+    @staticmethod
+    def batch(frames):
+        """Equally sized frames of one decode call as the (n, h, w, 3) view of their shared buffer (no copy)."""
+        h, w, _ = frames[0].shape
+        if any(tuple(f.shape) != (h, w, 3) for f in frames):
+            raise ValueError("the frames differ in size")
+        return frames[0].as_strided((len(frames), h, w, 3), (h * w * 3, w * 3, 3, 1))
+
+
+_PNG_DECODERS = {}
+
+
+def png_decoder(device=None):
+    device = _png_device(device)
+    d = _PNG_DECODERS.get(device)
+    if d is None:
+        d = _PNG_DECODERS[device] = PngDecoder(device)
+    return d
+
+
+def decode_png(files, order="rgb", check_crc=False, device=None):
+    """PNG files (one `bytes` or a sequence) -> list of device uint8 (h, w, 3) frames, views of one buffer with dense rows.
+    order="bgr": cv2.imdecode's channel order, which the drivers hand unflipped to everything downstream.  check_crc: verify
+    every chunk's CRC-32 on the host first (zlib.crc32); the Adler-32 of the pixel stream is always checked on the device.
+    A file the device refuses raises hip.RcdmError naming the file index and the RCDM_PNG_E* code; one out of scope (bit
+    depth, Adam7, missing chunks) NotImplementedError.  There is no CPU path: without a GPU it raises."""
+    files = _png_files(files)
+    return png_decoder(device).decode(files, order, check_crc)
+
+
+def load_png(paths, order="rgb", check_crc=False, device=None):
+    """decode_png of the files at `paths` (a single path gives a list of one frame)."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    files = []
+    for p in paths:
+        with open(p, "rb") as f:
+            files.append(f.read())
+    return decode_png(files, order, check_crc, device)
