@@ -383,6 +383,8 @@ int rcdm_layernorm(const rcdm_layernorm_desc* d, const void* x, const float* gam
  *   A caller that cannot bound its scores below that sets RCDM_ATTN_WIDE_RANGE in `flags` (or the environment sets
  *   RCDM_ATTN_MSUB=0): the fp32-fma softmax kernel, which has neither limit.  rcdms_amd/engine.py sets it from a
  *   data-independent bound on |q| |k| (LayerNorm output norm x Frobenius norms of the folded per-head weights).
+ *   Rounding (rcdm_flash_attn, rcdm_flash_attn_masked and rcdm_xattn, every head dim): the probabilities are rounded toward
+ *   zero to f16 and normalised by the sum of the ROUNDED values, so a constant V column is reproduced exactly.
  * ---------------------------------------------------------------------------------------------- */
 #define RCDM_ATTN_WIDE_RANGE 1
 typedef struct {

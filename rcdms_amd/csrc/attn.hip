@@ -59,6 +59,11 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // ~4 VALU ops per score: raw v_exp_f32, v_max3 row max, packed RTZ f16 conversion, the row SUM taken from a
 // ones-row appended to V^T (it falls out of the PV MFMA, consistently with the rounded P), the O rescale skipped
 // while the running max does not move, and all K/V staging index math hoisted out of the key-tile loop.
+// Row-sum rule, both paths: O / l divides by the sum of the f16-ROUNDED P, the values the PV MFMA multiplies, so a constant
+// V column comes back exactly.  Where the padded head dim has no spare column for the ones-row (d = 32 DF with DS even:
+// d = 32 and d = 160) the sum is taken on the VALU out of the f16 P operand registers (v_dot2c_f32_f16 against ones: exact
+// products, fp32 accumulation, f16 subnormals kept) — never from the unrounded exponentials, which are larger by the RTZ
+// loss (a relative ~3e-4 on every output row).
 // MASKED: causal and/or key-padding mask (the stage-1 prior transformer's additive -10000 mask, myprior_transformer.py:
 // 389-393: a masked score contributes exp(-10000) = 0 in fp32, so masking hard to -inf is the same result).
 // NW waves per block (4: two blocks per CU; 8: one block of 256 queries per CU — every K/V tile is fetched from L2 and
@@ -348,13 +353,17 @@ __global__ __launch_bounds__(NW * 64, (MASKED && DS >= 5) ? 1 : 2) void flash_at
         m_issue[j] = m_next[j];
         continue;
       }
-      float m_new = fmaxf(m_run[j], mx * p.c);  // unmasked: every tile has >= 1 valid key, so m_new is finite
+      const float m_max = fmaxf(m_run[j], mx * p.c);  // unmasked: every tile has >= 1 valid key, so it is finite
+      float m_new = m_max;
       if constexpr (MASKED) {
-        if (m_new == -INFINITY) m_new = 0.f;  // nothing visible to this query so far: P = exp2(-inf - 0) = 0, not NaN
+        // nothing visible to this query so far: P = exp2(-inf - 0) = 0, not NaN.  The running max itself stays -inf, so the
+        // first VISIBLE score sets it: carried on as 0 it would stand in for a max the row never had, and a row whose
+        // scores all lie far below 0 would underflow f16 in every probability
+        if (m_max == -INFINITY) m_new = 0.f;
       }
-      const bool moved = m_new != m_run[j];
+      const bool moved = m_max != m_run[j];
       const float alpha = __builtin_amdgcn_exp2f(m_run[j] - m_new);  // first tile: exp2(-inf) = 0
-      m_run[j] = m_new;
+      m_run[j] = m_max;
       float lsum = 0.f;
 #pragma unroll
       for (int f = 0; f < 2; ++f)
@@ -362,11 +371,16 @@ __global__ __launch_bounds__(NW * 64, (MASKED && DS >= 5) ? 1 : 2) void flash_at
         for (int r = 0; r < 16; r += 2) {
           const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[j][f][r], p.c, -m_new));
           const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[j][f][r + 1], p.c, -m_new));
-          if (!ones_row) lsum += p0 + p1;
           const auto pk = __builtin_amdgcn_cvt_pkrtz(p0, p1);  // v_cvt_pkrtz_f16_f32: two f16 in one VALU op
           pf[j][f * 2 + (r >> 3)][r & 7] = (f16)pk[0];
           pf[j][f * 2 + (r >> 3)][(r & 7) + 1] = (f16)pk[1];
         }
+      if constexpr ((DS & 1) == 0) {  // the sum of what the P V product will see: the rounded P, out of the operand registers
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int e = 0; e < 8; e += 2) lsum = __builtin_amdgcn_fdot2(f16x2{pf[j][i][e], pf[j][i][e + 1]}, f16x2{1, 1}, lsum, false);
+      }
       if (__any(moved)) {  // wave-uniform: once the running max has settled the accumulators are left alone
         l_run[j] *= alpha;
 #pragma unroll
@@ -390,6 +404,9 @@ __global__ __launch_bounds__(NW * 64, (MASKED && DS >= 5) ? 1 : 2) void flash_at
         vf.h[1] = lds_read_tr16(vp + 8 * VR);
 #pragma unroll
         for (int j = 0; j < QF; ++j) oacc[j][f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf.v, pf[j][st], oacc[j][f], 0, 0, 0);
+        // d > 112: one step's V reads in flight at a time.  Left alone hipcc hoists ten steps' fragments above the MFMAs, which
+        // takes the unmasked kernel past its 256 registers (two blocks per CU) into scratch
+        if constexpr (DS == 10) __builtin_amdgcn_sched_barrier(0);
       }
     RCDM_ATTN_STAMP(tr_pv);
   };
@@ -487,7 +504,8 @@ int launch_flash(const AttnArgs& a_in, hipStream_t stream) {
 //   S^T = K Q^T     K fragments straight from global memory,
 //   softmax         one pass, lane-local + one exchange with lane ^ 32, no running max,
 //   O^T = V^T P^T   V^T fragments straight from global memory, a row of ones behind the head's last dim so the row sum
-//                   falls out of the same MFMA (consistent with the rounded P).
+//                   falls out of the same MFMA (consistent with the rounded P); at d = 32 and d = 160, where the padded
+//                   head dim has no spare row, the sum of the rounded P is taken on the VALU instead (same rule).
 // K and V of the context do not change over the denoising steps, so rcdm_xattn_pack_kv writes them ONCE per context as
 // a FRAGMENT-MAJOR image: every MFMA operand fragment is one contiguous 1-KiB block in lane order (lane l's eight halfs
 // at byte 16 l), i.e. one fully coalesced load instruction.  (A first version read the fragments out of the row-major
@@ -530,7 +548,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DS <= 3) ? 4 : 2) void xattn_k
   const int npb = (nqb + qi - 1) / qi;          // blocks per (batch, head)
   const int bh = blockIdx.x / npb, qb0 = (blockIdx.x - bh * npb) * qi;
   const int b = bh / p.heads, h = bh - b * p.heads;
-  const bool ones_row = p.d < 32 * DF;
+  const bool ones_row = (DS & 1) ? true : p.d < 32 * DF;   // odd DS: d <= 16 DS < 32 DF, a spare row always
   constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   {
     const uint4* srck = (const uint4*)(p.KF + (size_t)bh * 3 * DS * 512);
@@ -605,11 +623,17 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DS <= 3) ? 4 : 2) void xattn_k
     for (int r = 0; r < 16; r += 2) {
       const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][r], p.c, -m));
       const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][r + 1], p.c, -m));
-      if (!ones_row) lsum += p0 + p1;
       const auto pk = __builtin_amdgcn_cvt_pkrtz(p0, p1);
       pf[kt * 2 + (r >> 3)][r & 7] = (f16)pk[0];
       pf[kt * 2 + (r >> 3)][(r & 7) + 1] = (f16)pk[1];
     }
+
+  if (!ones_row) {  // the sum of what the P V product will see: the rounded P, out of the operand registers
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) lsum = __builtin_amdgcn_fdot2(f16x2{pf[i][e], pf[i][e + 1]}, f16x2{1, 1}, lsum, false);
+  }
 
   // ---- O^T = V^T P^T: six steps of 16 keys per dim tile
   f32x16 oacc[DF];

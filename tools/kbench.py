@@ -141,7 +141,7 @@ def bench_attn(rounds, only=""):
     for name, batch, heads, L, Lk, d in [("L0 self d=40", 10, 8, 4096, 4096, 40), ("L1 self d=80", 10, 8, 1024, 1024, 80),
                                           ("L2 self d=160", 10, 8, 256, 256, 160), ("L0 cross Lk=85", 10, 8, 4096, 85, 40),
                                           ("L1 cross Lk=85", 10, 8, 1024, 85, 80), ("L2 cross Lk=85", 10, 8, 256, 85, 160),
-                                          ("L3 cross Lk=85", 10, 8, 64, 85, 160),
+                                          ("L3 cross Lk=85", 10, 8, 64, 85, 160), ("L3 self d=160", 10, 8, 64, 64, 160),
                                           # CLIP-bigG vision tower, 16 heads x 104 over 257 tokens (A/B: RCDM_ATTN_DS7=0 | 1)
                                           ("clip bigG d=104 B=1", 1, 16, 257, 257, 104),
                                           ("clip bigG d=104 B=5", 5, 16, 257, 257, 104)]:
