@@ -800,9 +800,9 @@ __global__ __launch_bounds__(512) void splitk_reduce_gn_kernel(const IgemmArgs p
   const int s = blockIdx.y, sp = blockIdx.x;
   const int r_begin = sp * p.gn_rps;
   const int r_end = min(p.gn_P, r_begin + p.gn_rps);
-  float sum[8], sq[8];
+  float S[8], Q[8], kp[8];   // shifted sums and their pivot (gn_plan.h): the thread's first STORED row, as gn_stats_kernel reads it
 #pragma unroll
-  for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
+  for (int e = 0; e < 8; ++e) S[e] = Q[e] = kp[e] = 0.f;
   const int n = ch * 8;
   // GN_U rows per thread and pass, as in gn_stats_kernel (the split is sized so that this is normally the block's only pass):
   // per slab, the loads of all GN_U rows are requested before the first addition — `splits` round trips per pass
@@ -850,18 +850,18 @@ __global__ __launch_bounds__(512) void splitk_reduce_gn_kernel(const IgemmArgs p
         float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (GEGLU gates: never with statistics)
         Pack16 o;
         o.u = epilogue_store(p, s * p.gn_P + ru, n, v[u], g);
+        if (u == 0 && r == r_begin + rl) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = (float)o.e[e];
-          sum[e] += f;
-          sq[e] += f * f;
+          for (int e = 0; e < 8; ++e) kp[e] = (float)o.e[e];
         }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gn_acc(S[e], Q[e], (float)o.e[e], kp[e], true);
       }
     }
   }
   GnArgs ga{};
   ga.partial = p.gn_partial; ga.G = p.gn_G; ga.cg = p.gn_cg; ga.CH = p.gn_CH; ga.RPB = p.gn_RPB; ga.splits = p.gn_splits;
-  gn_block_partials(ga, part, t, sum, sq, s, sp, r_end - r_begin);
+  gn_block_partials(ga, part, t, S, Q, kp, s, sp, r_end - r_begin);
 }
 
 // the reduce launch of a split-K GEMM / conv (every kernel family writes the same [split][M][N] fp32 slabs)

@@ -22,30 +22,42 @@ __global__ void gn_stats_kernel(const GnArgs p) {
   const int s = blockIdx.y, sp = blockIdx.x;
   const int r_begin = sp * p.rows_per_split;
   const int r_end = min(p.P, r_begin + p.rows_per_split);
-  float sum[8], sq[8];
+  // shifted sums and their pivot (gn_plan.h): the thread's first row.  fp32 pairs (v_pk_add_f32 / v_pk_fma_f32: the same IEEE
+  // operations as gn_acc, two per instruction); a row past r_end is read as the pivot row again, which adds exact zeros
+  f32x2 S2[4], Q2[4], k2[4];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
+  for (int j = 0; j < 4; ++j) S2[j] = Q2[j] = k2[j] = f32x2{0.f, 0.f};
   const f16* base = p.x + (size_t)s * p.P * p.ldx + ch * 8;
   // GN_U independent 16-byte loads in flight per thread (the split is sized so that this is normally the block's ONE
-  // memory round trip: a launch this short is a chain of latencies, not a stream); rows past r_end add nothing
+  // memory round trip: a launch this short is a chain of latencies, not a stream)
   for (int r = r_begin + rl; r < r_end; r += GN_U * p.RPB) {
     Pack16 v[GN_U];
 #pragma unroll
     for (int u = 0; u < GN_U; ++u) {
       const int ru = r + u * p.RPB;
-      v[u].u = make_uint4(0, 0, 0, 0);
-      if (ru < r_end) v[u].u = *(const uint4*)(base + (size_t)ru * p.ldx);
+      v[u].u = *(const uint4*)(base + (size_t)(ru < r_end ? ru : r_begin + rl) * p.ldx);
+    }
+    if (r == r_begin + rl) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) k2[j] = f32x2{(float)v[0].e[2 * j], (float)v[0].e[2 * j + 1]};
     }
 #pragma unroll
     for (int u = 0; u < GN_U; ++u)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float f = (float)v[u].e[e];
-        sum[e] += f;
-        sq[e] += f * f;
+      for (int j = 0; j < 4; ++j) {
+        const f32x2 d = f32x2{(float)v[u].e[2 * j], (float)v[u].e[2 * j + 1]} - k2[j];
+        S2[j] += d;
+        Q2[j] = __builtin_elementwise_fma(d, d, Q2[j]);
       }
   }
-  gn_block_partials(p, part, t, sum, sq, s, sp, r_end - r_begin);
+  float S[8], Q[8], k[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    S[2 * j] = S2[j].x; S[2 * j + 1] = S2[j].y;
+    Q[2 * j] = Q2[j].x; Q[2 * j + 1] = Q2[j].y;
+    k[2 * j] = k2[j].x; k[2 * j + 1] = k2[j].y;
+  }
+  gn_block_partials(p, part, t, S, Q, k, s, sp, r_end - r_begin);
 }
 
 // one wave per (sample, group): lanes take splits lane, lane+64, ... in order, then a fixed xor-butterfly
@@ -217,9 +229,11 @@ __global__ void gn_apply_kernel(const GnArgs p) {
 // Single-launch GroupNorm for the smallest levels (16x16 per frame, 8x8: 30 of the 81 GroupNorms of a UNet call).  There the
 // tensor is a few MB, the three-launch form is mostly launch latency (a dependent graph node costs >= 1.6 us even when
 // empty), and one block can own a whole (sample, group-bundle) slab: block (bundle, sample) covers GB consecutive groups
-// = NCHK whole 16-byte chunks of every row (GB chosen so that GB * cg is a multiple of 8), sums x and x^2 over the slab
+// = NCHK whole 16-byte chunks of every row (GB chosen so that GB * cg is a multiple of 8), takes the slab's moments
 // (thread-sequential, then a fixed-order LDS reduction: deterministic), and applies (+SiLU) reading the slab again
-// from L2.  Same arithmetic as one split of gn_stats + gn_finalize + gn_apply.
+// from L2.  The statistics are the shifted moments of gn_plan.h over the whole slab (the helpers of gn_stats, with this kernel's
+// thread geometry: no partials and no Chan step across splits, so the results agree to rounding, not bit for bit); the apply
+// pass is gn_apply's arithmetic.
 struct GnFusedArgs {
   const f16* x;
   f16* y;
@@ -240,53 +254,55 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const GnFusedArgs p) {
   const int s = blockIdx.y, c0 = blockIdx.x * p.GB * p.cg;  // first channel of this bundle
   const f16* xb = p.x + (size_t)s * p.P * p.ldx + c0 + ch * 8;
   f16* yb = p.y + (size_t)s * p.P * p.ldy + c0 + ch * 8;
-  float sum[8], sq[8];
+  // shifted sums and their pivot (gn_plan.h): the thread's first row; fp32 pairs, a row past P read as the pivot row again
+  // (exact zeros), as in gn_stats_kernel
+  f32x2 S2[4], Q2[4], k2[4];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
+  for (int j = 0; j < 4; ++j) S2[j] = Q2[j] = k2[j] = f32x2{0.f, 0.f};
   if (live) {
     for (int r = rl; r < p.P; r += 4 * p.RPB) {
       Pack16 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int ru = r + u * p.RPB;
-        v[u].u = make_uint4(0, 0, 0, 0);
-        if (ru < p.P) v[u].u = *(const uint4*)(xb + (size_t)ru * p.ldx);
+        v[u].u = *(const uint4*)(xb + (size_t)(ru < p.P ? ru : rl) * p.ldx);
+      }
+      if (r == rl) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k2[j] = f32x2{(float)v[0].e[2 * j], (float)v[0].e[2 * j + 1]};
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = (float)v[u].e[e];
-          sum[e] += f;
-          sq[e] += f * f;
+        for (int j = 0; j < 4; ++j) {
+          const f32x2 d = f32x2{(float)v[u].e[2 * j], (float)v[u].e[2 * j + 1]} - k2[j];
+          S2[j] += d;
+          Q2[j] = __builtin_elementwise_fma(d, d, Q2[j]);
         }
     }
   }
+  float S[8], Q[8], k[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    part[t * 16 + e] = sum[e];
-    part[t * 16 + 8 + e] = sq[e];
+  for (int j = 0; j < 4; ++j) {
+    S[2 * j] = S2[j].x; S[2 * j + 1] = S2[j].y;
+    Q[2 * j] = Q2[j].x; Q[2 * j + 1] = Q2[j].y;
+    k[2 * j] = k2[j].x; k[2 * j + 1] = k2[j].y;
+  }
+  {
+    const float m = live ? gn_rows_of(rl, p.P, p.RPB) : 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gn_shifted_moments(S[e], Q[e], k[e], m, part[t * 16 + e], part[t * 16 + 8 + e]);
   }
   __syncthreads();
-  // column sums first (NCHK * 16 values, each over the RPB row-threads, spread over the block), then the few groups
+  // column moments first (NCHK * 8 columns, each over the RPB row-threads, spread over the block), then the few groups
   __shared__ float colsum[32 * 16];
-  for (int o = t; o < p.NCHK * 16; o += 256) {
-    const int c = o >> 4, k = o & 15;
-    float a = 0.f;
-    for (int r = 0; r < p.RPB; ++r) a += part[(r * p.NCHK + c) * 16 + k];
-    colsum[o] = a;
-  }
+  gn_column_moments(part, colsum, p.NCHK, p.RPB, p.P, t, 256);
   __syncthreads();
   if (t < p.GB) {
-    float gs = 0.f, gq = 0.f;
-    for (int c = t * p.cg; c < (t + 1) * p.cg; ++c) {
-      gs += colsum[(c >> 3) * 16 + (c & 7)];
-      gq += colsum[(c >> 3) * 16 + 8 + (c & 7)];
-    }
+    float mean, m2;
+    gn_group_moments([&](int c) { return colsum[(c >> 3) * 16 + (c & 7)]; }, [&](int c) { return colsum[(c >> 3) * 16 + 8 + (c & 7)]; },
+                     t * p.cg, p.cg, (float)p.P, mean, m2);
     const float n = (float)p.P * (float)p.cg;
-    const float mean = gs / n;
-    float m2 = gq - gs * mean;
-    if (m2 < 0.f) m2 = 0.f;
     gstat[t * 2] = mean;
     gstat[t * 2 + 1] = rsqrtf(m2 / n + p.eps);  // biased variance, as torch.nn.GroupNorm
     if (p.stat_out) {

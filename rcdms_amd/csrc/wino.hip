@@ -28,6 +28,7 @@
 #include "igemm_args.h"
 #include "pp_sync.h"
 #include "igemm_epilogue.h"
+#include "gn_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -298,8 +299,8 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs p) {
 // group (each the fixed-order sum of its split-K slabs), A^T M A, + the four 1x1 terms, + bias + row vector, + residual, x scale.
 // SP: split count compiled in (1, 2: all slab loads requested before the first addition), 0 = any (one round trip per slice).
 // go_partial: the block also leaves the tile's partial statistics for the GroupNorm that reads `out` next — taken from the
-// STORED halfs (what a statistics pass would read back), per-channel sums through LDS, then one thread per group in channel
-// order: deterministic.
+// STORED halfs (what a statistics pass would read back) as shifted moments (gn_plan.h), per-channel (mean, M2) through LDS,
+// then one thread per group in channel order: deterministic.
 template <bool S16>
 __device__ __forceinline__ f32x4 slab_load4(const WinoArgs& p, size_t off) {
   if constexpr (S16) {
@@ -379,22 +380,29 @@ __global__ __launch_bounds__(512) void wino_out_kernel(const WinoArgs p) {
     f32x4 add = {0.f, 0.f, 0.f, 0.f};
     if (p.epi & RCDM_EPI_BIAS) add += *(const f32x4*)(p.bias + n);
     if (p.epi & RCDM_EPI_ROWVEC) add += *(const f32x4*)(p.rowvec + (size_t)(prow[0] / p.rows_per_sample) * p.ldt + n);   // (a tile lies inside one image)
-    f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cq = cs;
+    float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f}, ck[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ab = 0; ab < 4; ++ab) {
       H4 q;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         q.e[e] = (f16)((o[ab][e] + add[e] + (float)rr[ab].e[e]) * p.out_scale);
-        const float f = (float)q.e[e];
-        cs[e] += f;
-        cq[e] += f * f;
+        if (ab == 0) ck[e] = (float)q.e[e];   // the pivot of the shifted sums (gn_plan.h): the tile's first pixel
+        gn_acc(cs[e], cq[e], (float)q.e[e], ck[e], true);
       }
       *(uint2*)(p.out + (size_t)prow[ab] * p.ldc + n) = q.u;
     }
-    if (p.go_partial) {   // per-channel (sum, sum of squares) over the tile's four pixels
-      *(f32x4*)(smem + (size_t)n * 4) = cs;
-      *(f32x4*)(smem + (size_t)(p.N + n) * 4) = cq;
+    if (p.go_partial) {   // per-channel (mean, M2) over the tile's four pixels
+      f32x4 cm, c2;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float mean, m2;
+        gn_shifted_moments(cs[e], cq[e], ck[e], 4.f, mean, m2);
+        cm[e] = mean;
+        c2[e] = m2;
+      }
+      *(f32x4*)(smem + (size_t)n * 4) = cm;
+      *(f32x4*)(smem + (size_t)(p.N + n) * 4) = c2;
     }
   }
   if (p.go_partial) {
@@ -402,15 +410,9 @@ __global__ __launch_bounds__(512) void wino_out_kernel(const WinoArgs p) {
     const int g = threadIdx.x;
     if (g < p.go_G) {
       const float* fs = (const float*)smem;
-      float gs = 0.f, gq = 0.f;
-      for (int c = g * p.go_cg; c < (g + 1) * p.go_cg; ++c) {
-        gs += fs[c];
-        gq += fs[p.N + c];
-      }
       const float nn = 4.f * (float)p.go_cg;
-      const float mean = gs / nn;
-      float m2 = gq - gs * mean;
-      if (m2 < 0.f) m2 = 0.f;
+      float mean, m2;
+      gn_group_moments([&](int c) { return fs[c]; }, [&](int c) { return fs[p.N + c]; }, g * p.go_cg, p.go_cg, 4.f, mean, m2);
       const int s = prow[0] / p.go_rps;
       const int sp = t - s * p.go_splits;
       float* o = p.go_partial + (((size_t)s * p.go_G + g) * p.go_splits + sp) * 3;
