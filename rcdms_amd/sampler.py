@@ -288,11 +288,16 @@ class PriorLoop:
     assembly | ~600 transformer launches | CFG combine + UnCLIP step | step++].  The scheduler's noise for all T steps is
     drawn up front (from the caller's generator, or supplied), so the captured step is a pure function of device state."""
 
-    def __init__(self, prior, frames, num_text_tokens, guidance_scale, scheduler, num_steps):
+    def __init__(self, prior, frames, num_text_tokens, guidance_scale, scheduler, num_steps, stories=1):
+        """stories: S stories per replay — n = frames * S latent rows in the order (s f), the CFG batch
+        [uncond: s0 f0..4, s1 f0..4, ...; cond: the same], so batch row r * S + s holds the 5 frames of story s."""
         self.prior = prior
         self.gs = float(guidance_scale)
         self.reps = 2 if guidance_scale > 1.0 else 1   # do_classifier_free_guidance, prior_pipeline.py:236-238
-        self.n = int(frames)
+        self.S = int(stories)
+        if self.S < 1:
+            raise ValueError(f"stories must be >= 1, got {stories}")
+        self.n = int(frames) * self.S
         self.T = int(num_steps)
         dev = prior.device
         self.device = dev

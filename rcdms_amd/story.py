@@ -1,0 +1,222 @@
+"""Story batches: S stories through stage 1 and stage 2 in one process.
+
+The reference runs a test set as two processes — stage1_batchtest_rcdms_model.py writes `{index}_{j}.npy` embeddings,
+stage2_batchtest_rcdms_model.py reads them back — one story per pipeline call.  Here:
+  * the helpers both public pipelines use for their story axis (a `prompt` of S lists of five captions): the argument
+    checks and `place_story_rows`, which puts every story's CFG rows where the captured loops expect them;
+  * `write_stage1_embeds`, the files of stage1…:260,264 for a stage-2 process of the old kind;
+  * `StoryRunner`: uint8 frames + captions -> CLIP vision forward -> stage 1 -> cosine figure -> hand-off -> stage 2,
+    batched over S, all tensors staying on the device.
+The hot paths are the two captured loops (rcdms_amd.sampler) at batch S; this module is glue around them."""
+import os
+from dataclasses import dataclass
+from typing import Any, Optional
+
+import numpy as np
+import torch
+
+FRAMES = 5
+
+
+# ---- the story axis of the two pipelines ---------------------------------------------------------------------------------
+
+def story_count(prompt, frames=FRAMES):
+    """None for a call in the single-story form (a string, or a flat list of strings); S for a list of S lists of `frames`
+    strings.  Anything in between — flat and nested entries mixed, a story with another number of captions, no story at
+    all — is a ValueError."""
+    if not isinstance(prompt, (list, tuple)):
+        return None
+    nested = [isinstance(p, (list, tuple)) for p in prompt]
+    if not any(nested):
+        return None
+    if not all(nested):
+        raise ValueError("`prompt` mixes captions and lists of captions: pass either a flat list of captions (one story) or a "
+                         "list of S lists (S stories)")
+    for s, story in enumerate(prompt):
+        if len(story) != frames or not all(isinstance(c, str) for c in story):
+            raise ValueError(f"`prompt[{s}]` must hold {frames} caption strings, one per frame, got {len(story)} entries")
+    return len(prompt)
+
+
+def check_story_axis(name, value, shape):
+    """ValueError unless `value` is a tensor of exactly `shape` (whose leading entry is the story count)."""
+    got = tuple(value.shape) if hasattr(value, "shape") else None
+    if got != tuple(shape):
+        raise ValueError(f"`{name}` must be {tuple(shape)} for {shape[0]} stories, got "
+                         f"{got if got is not None else type(value).__name__}")
+
+
+def story_generators(generator, stories):
+    """One generator per story: a list of S generators as given, one generator (or None) for every story — the S stories
+    then draw from it one after the other, as S single-story calls would."""
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != stories:
+            raise ValueError(f"a list of {len(generator)} generators for {stories} stories: pass one generator, or one per story")
+        return list(generator)
+    return [generator] * stories
+
+
+def place_story_rows(rows, reps, frames=FRAMES):
+    """rows: S tensors (reps * frames, ...), story s's rows as the single-story call builds them (CFG half r, frame f at row
+    r * frames + f).  -> (reps * S * frames, ...) in the order of the captured loops, whose batch row is r * S + s
+    (rcdms_amd.sampler.DenoiseLoop): out[(r * S + s) * frames + f] = rows[s][r * frames + f].  S = 1 is the identity."""
+    S = len(rows)
+    for s, t in enumerate(rows):
+        if t.shape[0] != reps * frames or t.shape[1:] != rows[0].shape[1:]:
+            raise ValueError(f"story {s} holds rows {tuple(t.shape)}, expected ({reps * frames}, ...) like story 0 "
+                             f"{tuple(rows[0].shape)}")
+    x = torch.stack(list(rows))                                       # (S, reps * frames, ...)
+    x = x.reshape(S, reps, frames, *x.shape[2:]).transpose(0, 1)      # (reps, S, frames, ...)
+    return x.reshape(reps * S * frames, *x.shape[3:])
+
+
+def write_stage1_embeds(save_dir, index, embeds):
+    """The files the stage-1 driver leaves for story `index` (stage1_batchtest_rcdms_model.py:260,264): `{index}_{j}.npy`,
+    the fp32 embedding (E,) of frame j, j = 0..4, and `{index}.npy`, all five (5, E).  The stage-2 driver reads
+    `{index}_{1..4}.npy` back (stage2_batchtest_rcdms_model.py:291-294).  -> the paths written."""
+    e = embeds.detach().to("cpu", torch.float32).numpy() if isinstance(embeds, torch.Tensor) else np.asarray(embeds, np.float32)
+    if e.ndim != 2 or e.shape[0] != FRAMES:
+        raise ValueError(f"a story's embeddings are ({FRAMES}, E), got {e.shape}")
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for j in range(FRAMES):
+        paths.append(os.path.join(save_dir, f"{index}_{j}.npy"))
+        np.save(paths[-1], np.ascontiguousarray(e[j]))
+    paths.append(os.path.join(save_dir, f"{index}.npy"))
+    np.save(paths[-1], np.ascontiguousarray(e))
+    return paths
+
+
+# ---- stage 1 -> stage 2 --------------------------------------------------------------------------------------------------
+
+@dataclass
+class StoryResult:
+    videos: Any                       # by output_type; None when stage 2 did not run
+    image_embeds: torch.Tensor        # (S, 5, E) stage-1 output
+    target_embeds: torch.Tensor       # (S, 5, E) CLIP embeddings of the five given frames
+    cosine: torch.Tensor              # (S, 5) the figure the stage-1 driver prints (:239,258)
+
+
+class StoryRunner:
+    """What the two drivers do per story (stage1…:146-261, stage2…:267-376), for S stories per call.
+
+    prior_pipe: Seq_Inpaint_Prior_Pipeline; stage2_pipe: RCDMsPipeline (None: stage 1 only); image_encoder: the CLIP vision
+    tower with projection (`.image_embeds`, `.last_hidden_state`); clip_processor: frames -> pixel values (default
+    rcdms_amd.image.ClipImageProcessor at the encoder's image size); frame_transform: frames -> stage-2 source frames in
+    [-1, 1] (default rcdms_amd.image.FrameTransform at the UNet's sample size)."""
+
+    def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None):
+        self.prior_pipe, self.stage2_pipe, self.image_encoder = prior_pipe, stage2_pipe, image_encoder
+        if clip_processor is None:
+            from .image import ClipImageProcessor
+            size = int(image_encoder.config.image_size)
+            clip_processor = ClipImageProcessor(size=size, crop_size=size)
+        if frame_transform is None and stage2_pipe is not None:
+            from .image import FrameTransform
+            side = stage2_pipe.unet.config.sample_size * stage2_pipe.vae_scale_factor
+            frame_transform = FrameTransform(side, side)
+        self.clip_processor, self.frame_transform = clip_processor, frame_transform
+        self._black_white = None
+
+    @property
+    def device(self):
+        return self.prior_pipe.device
+
+    def _pixels(self, frames):
+        return self.clip_processor(images=frames, return_tensors="pt").pixel_values
+
+    def black_white_embeds(self, like):
+        """(black, white): `image_embeds` (E,) of the all-black and the all-white image (stage1…:160-163), encoded once per
+        runner — the drivers encode them again for every story.  like: uint8 frames (n, H, W, 3) giving size and device."""
+        if self._black_white is None:
+            bw = torch.zeros(2, *like.shape[1:], dtype=torch.uint8, device=like.device)
+            bw[1] = 255
+            e = self.image_encoder(self._pixels(bw)).image_embeds
+            self._black_white = (e[0].clone(), e[1].clone())
+        return self._black_white
+
+    def stage1_inputs(self, target, black, white, mode, done=None):
+        """(imgs_proj_embeds1, mask_label), each (S, 5, 1, E).  done None: the mode's own rows (stage1…:164-178) —
+        "continue": [frame 0, black x 4] under the mask [white, black x 4]; "visualization": black throughout.  done
+        (S, i, E), i >= 1: pass i of the autoregressive loop (:190-224) — the i embeddings generated so far, then black, under
+        a mask whose first i entries are white."""
+        S, E = target.shape[0], target.shape[-1]
+        proj = black.expand(S, FRAMES, E).clone()
+        label = black.expand(S, FRAMES, E).clone()
+        if done is not None:
+            i = done.shape[1]
+            proj[:, :i] = done
+            label[:, :i] = white
+        elif mode == "continue":
+            proj[:, 0] = target[:, 0]
+            label[:, 0] = white
+        return proj.unsqueeze(2), label.unsqueeze(2)
+
+    @torch.no_grad()
+    def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
+                 guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
+                 save_dir=None, indices=None, stage2=None, fix_context_order=False):
+        """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
+        drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
+        indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1)."""
+        if mode not in ("continue", "visualization"):
+            raise ValueError("check mode")                                      # stage1…:180
+        if stage2 is None:
+            stage2 = mode == "continue" and self.stage2_pipe is not None
+        if stage2 and mode == "visualization":
+            raise ValueError('stage 2 in mode "visualization": the reference leaves image_embeds_1 / proj_embeds_0 undefined '
+                             "there and fails at stage2_batchtest_rcdms_model.py:367 — run mode=\"continue\", or stage2=False")
+        if stage2 and self.stage2_pipe is None:
+            raise ValueError("stage 2 asked for, but the runner was built without a stage-2 pipeline")
+        frames = torch.as_tensor(frames)
+        if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[1] != FRAMES or frames.shape[-1] != 3:
+            raise ValueError(f"frames are uint8 (S, {FRAMES}, H, W, 3), got {frames.dtype} {tuple(frames.shape)}")
+        S = frames.shape[0]
+        if story_count(texts) != S:
+            raise ValueError(f"`texts` must be {S} lists of {FRAMES} captions, one list per story of `frames`")
+        indices = list(range(S)) if indices is None else list(indices)
+        if len(indices) != S:
+            raise ValueError(f"{len(indices)} indices for {S} stories")
+        texts = [[c.lower() for c in story] for story in texts]
+        frames = frames.to(self.device)
+
+        # one vision forward over the 5 * S target frames: targets, stage 1's source_clip[0], stage 2's image_embeds_1
+        vis = self.image_encoder(self._pixels(frames.reshape(S * FRAMES, *frames.shape[2:])))
+        target = vis.image_embeds.reshape(S, FRAMES, -1)
+        black, white = self.black_white_embeds(frames[0])
+
+        def prior(proj, label):
+            return self.prior_pipe(prompt=texts, imgs_proj_embeds1=proj, mask_label=label, video_length=FRAMES,
+                                   guidance_scale=prior_guidance_scale, generator=prior_generator,
+                                   num_inference_steps=prior_steps).image_embeds
+
+        if autoreg:
+            # five passes (stage1…:186-242): pass i conditions on the rows kept from passes 0..i-1 and keeps its row i
+            kept = []
+            for i in range(FRAMES):
+                out = prior(*self.stage1_inputs(target, black, white, mode, torch.stack(kept, dim=1) if kept else None))
+                kept.append(out[:, i].to(target.dtype))
+            embeds = torch.stack(kept, dim=1)
+        else:
+            embeds = prior(*self.stage1_inputs(target, black, white, mode))
+        embeds = embeds.float()
+        cosine = torch.nn.functional.cosine_similarity(embeds, target.float(), dim=-1)
+        if save_dir is not None:
+            for s, index in enumerate(indices):
+                write_stage1_embeds(save_dir, index, embeds[s])
+        videos = None
+        if stage2:
+            pipe, ft = self.stage2_pipe, self.frame_transform
+            H, W = ft.height, ft.width
+            h, w = H // pipe.vae_scale_factor, W // pipe.vae_scale_factor
+            source = torch.full((S, FRAMES, 3, H, W), -1.0, dtype=torch.float32, device=self.device)   # mask_augment(black)
+            source[:, 0] = ft(frames[:, 0])
+            label = torch.zeros(S, FRAMES, h, w, dtype=torch.float32, device=self.device)
+            label[:, 0] = 1.0
+            hidden = vis.last_hidden_state.reshape(S, FRAMES, *vis.last_hidden_state.shape[1:])
+            videos = pipe(prompt=texts, source_img=source, image_embeds_1=[hidden[s, :1] for s in range(S)],
+                          proj_embeds_0=[embeds[s, 1:].unsqueeze(1) for s in range(S)], mask_label=label,
+                          video_length=FRAMES, height=H, width=W, guidance_scale=guidance_scale, generator=generator,
+                          num_inference_steps=num_inference_steps, output_type=output_type,
+                          fix_context_order=fix_context_order).videos
+        return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine)

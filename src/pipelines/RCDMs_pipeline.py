@@ -9,7 +9,8 @@ What runs where:
     does (they are inputs of this pipeline, not part of it).
 Reference quirks kept by default: exactly 5 frames per story, batch 1 per call, and the context
 rows re-joined as cat([seen, unseen]) (:450) — pass fix_context_order=True to restore (b f) row order.
-Generalised: any (height, width) divisible by 64, CFG on or off."""
+Generalised: any (height, width) divisible by 64, CFG on or off; a `prompt` of S lists of five captions runs S stories through
+one captured loop (`_call_stories`), each computing what its single-story call computes."""
 import inspect
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Union
@@ -19,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from rcdms_amd.sampler import DenoiseLoop
+from rcdms_amd.story import check_story_axis, place_story_rows, story_count, story_generators
 from ..models.unet import UNet3DConditionModel, _Config
 
 
@@ -182,12 +184,28 @@ class RCDMsPipeline:
             ctx = fixed
         return ctx
 
+    # One VAE launch plan holds at most this many pixels: the convolution kernels address an activation through 32-bit byte
+    # offsets (RCDM_ESHAPE beyond 2 GB: 16 frames of 512 x 512 at the SD-1.5 VAE's 256 f16 channels at full resolution).  Two
+    # stories at 512 x 512 is the largest plan that has been run; 5 * S frames beyond it go in runs of whole stories.
+    VAE_PIXELS_PER_CALL = 10 * 512 * 512
+
+    def _vae_chunks(self, x, scale=1):
+        """x (n, c, h, w), n a multiple of the 5 frames of a story (`scale`: pixels per entry of h and w) -> x in the fewest
+        runs of whole stories whose frames hold at most VAE_PIXELS_PER_CALL pixels, one story at the least: [x] for a single
+        story at any size, and for any batch of small frames."""
+        n, f = x.shape[0], self.FRAMES
+        px = f * x.shape[2] * x.shape[3] * scale * scale
+        per = f * max(1, self.VAE_PIXELS_PER_CALL // px)
+        if n <= per or n % f:
+            return [x]
+        return [x[i:i + per] for i in range(0, n, per)]
+
     def decode_latents(self, latents):
         """(:274-287) one frame at a time through the user's VAE."""
         f = latents.shape[2]
         latents = (1 / 0.18215 * latents).permute(0, 2, 1, 3, 4).reshape(-1, latents.shape[1], *latents.shape[3:])
         if self.vae_decoder is not None:
-            video = self.vae_decoder.decode(latents).sample
+            video = torch.cat([self.vae_decoder.decode(z).sample for z in self._vae_chunks(latents, self.vae_scale_factor)])
         else:
             frames = [self.vae.decode(latents[i:i + 1]).sample for i in range(latents.shape[0])]
             video = torch.cat(frames)
@@ -202,7 +220,7 @@ class RCDMsPipeline:
         f = latents.shape[2]
         latents = (1 / 0.18215 * latents).permute(0, 2, 1, 3, 4).reshape(-1, latents.shape[1], *latents.shape[3:])
         if self.vae_decoder is not None:
-            frames = self.vae_decoder.decode_uint8(latents)
+            frames = torch.cat([self.vae_decoder.decode_uint8(z) for z in self._vae_chunks(latents, self.vae_scale_factor)])
         else:
             frames = frames_to_uint8(torch.cat([self.vae.decode(latents[i:i + 1]).sample for i in range(latents.shape[0])]))
         return frames.reshape(-1, f, *frames.shape[1:])
@@ -243,7 +261,7 @@ class RCDMsPipeline:
 
     # ---- the hot loop ----------------------------------------------------------------------------------------------
     def denoise(self, latents, mask, masked_latents, context, num_inference_steps, guidance_scale, callback=None,
-                callback_steps=1, generator=None):
+                callback_steps=1, generator=None, noise=None):
         """latents (S,4,f,h,w) unit-variance noise (DenoiseLoop.load applies init_noise_sigma); mask (R*S,1,f,h,w);
         masked_latents (R*S,4,f,h,w); context (R*S*f, L, D); generator: the per-step noise of Euler-ancestral."""
         S, _, f, h, w = latents.shape
@@ -254,7 +272,7 @@ class RCDMsPipeline:
                                      num_inference_steps)
             self._loop_key = (S, f, h, w, context.shape[1], float(guidance_scale), int(num_inference_steps),
                               id(self.scheduler), id(self.unet), self.unet._weights_gen)
-        self._loop.load(latents, mask, masked_latents, context, generator=generator)
+        self._loop.load(latents, mask, masked_latents, context, noise=noise, generator=generator)
         return self._loop.run(callback=callback, callback_steps=callback_steps)
 
     @torch.no_grad()
@@ -272,6 +290,11 @@ class RCDMsPipeline:
             raise NotImplementedError("eta > 0 is not used by the reference and has no fused HIP step")
         if video_length != self.FRAMES:
             raise ValueError(f"a story has exactly {self.FRAMES} frames (reference RCDMs_pipeline.py:261,430,476)")
+        if story_count(prompt, video_length) is not None:
+            return self._call_stories(prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
+                                      num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator,
+                                      latents, output_type, return_dict, callback, callback_steps, fix_context_order,
+                                      png_match)
         batch_size = 1
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -302,6 +325,14 @@ class RCDMsPipeline:
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         mask5 = masked_label.view(reps, 1, self.FRAMES, h, w)   # the reference hard-codes (2,1,5,64,64) at :476
 
+        return self._sample_and_decode(latents, mask5, masked_latents, context, text_embeddings.dtype, num_inference_steps,
+                                       guidance_scale, generator, None, callback, callback_steps, output_type, return_dict,
+                                       png_match)
+
+    def _sample_and_decode(self, latents, mask5, masked_latents, context, dtype, num_inference_steps, guidance_scale,
+                           generator, noise, callback, callback_steps, output_type, return_dict, png_match):
+        """The captured loop on the staged inputs, then the VAE decode by `output_type` (:455-513); the batch axis of
+        `latents` is the story axis."""
         with self.progress_bar(total=num_inference_steps) as bar:
             def on_step(i, t, lat):
                 bar.update()
@@ -310,24 +341,104 @@ class RCDMsPipeline:
             # prepare_latents applied init_noise_sigma (as the reference does); DenoiseLoop.load applies it itself
             final = self.denoise(latents / self.scheduler.init_noise_sigma, mask5, masked_latents, context,
                                  num_inference_steps, guidance_scale, callback=on_step if (callback is not None) else None,
-                                 callback_steps=1, generator=generator)
+                                 callback_steps=1, generator=generator, noise=noise)
             if callback is None:
                 bar.update(num_inference_steps)
 
         if output_type in ("uint8", "png"):
-            video = self.decode_latents_uint8(final.to(text_embeddings.dtype))
+            video = self.decode_latents_uint8(final.to(dtype))
             if output_type == "png":                       # [[bytes] * f] * b: one PNG file per frame, encoded on the device
                 from rcdms_amd.image import encode_png
                 b, f = video.shape[:2]
                 files = encode_png(video.reshape(b * f, *video.shape[2:]), match=png_match)
                 video = [files[i * f:(i + 1) * f] for i in range(b)]
             return RCDMsPipelineOutput(videos=video) if return_dict else video
-        video = self.decode_latents(final.to(text_embeddings.dtype))
+        video = self.decode_latents(final.to(dtype))
         if output_type == "tensor":
             video = torch.from_numpy(video)
         if not return_dict:
             return video
         return RCDMsPipelineOutput(videos=video)
+
+    def _call_stories(self, prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
+                      num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator, latents,
+                      output_type, return_dict, callback, callback_steps, fix_context_order, png_match):
+        """`prompt` is S lists of five captions: S stories through one captured loop.  Story s is the single-story call on
+        story s's inputs with story s's generator (one generator: the S calls made one after the other with it).  Every
+        story's ten context rows and mask rows are built as in that call and then placed at the loop's batch rows r * S + s
+        (rcdms_amd.story.place_story_rows); the prompts take one text-encoder call and the 5 * S source frames one VAE
+        encode.  source_img (S, 5, 3, H, W), mask_label (S, 5, h, w), image_embeds_1 / proj_embeds_0 lists of S tensors,
+        latents (S, 4, 5, h, w) -> videos (S, 3, 5, H, W)."""
+        f = self.FRAMES
+        S = story_count(prompt, f)
+        if num_videos_per_prompt != 1:
+            raise NotImplementedError("num_videos_per_prompt != 1 with a story axis")
+        h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        check_story_axis("source_img", source_img, (S, f, 3, height, width))
+        check_story_axis("mask_label", mask_label, (S, f, h, w))
+        for name, v in (("image_embeds_1", image_embeds_1), ("proj_embeds_0", proj_embeds_0)):
+            if not isinstance(v, (list, tuple)) or len(v) != S:
+                raise ValueError(f"`{name}` is a list of {S} tensors, one per story (the seen-frame count may differ), got "
+                                 f"{type(v).__name__}" + (f" of length {len(v)}" if isinstance(v, (list, tuple)) else ""))
+        if latents is not None:
+            check_story_axis("latents", latents, (S, 4, f, h, w))
+        gens = story_generators(generator, S)
+        device = self._execution_device
+        cfg_on = guidance_scale > 1.0
+        reps = 2 if cfg_on else 1
+
+        flat = [c for story in prompt for c in story]
+        if isinstance(negative_prompt, list):
+            if story_count(negative_prompt, f) != S:
+                raise ValueError(f"`negative_prompt` must be one string or {S} lists of {f} strings, as `prompt`")
+            negative_prompt = [c for story in negative_prompt for c in story]
+        elif negative_prompt is not None:
+            negative_prompt = [negative_prompt] * (S * f)
+        # rows [uncond: s0 f0..4, s1 f0..4, ...; cond: the same]
+        text = self._encode_prompt(flat, device, 1, cfg_on, negative_prompt)
+        dt = text.dtype
+
+        src = source_img.reshape(S * f, *source_img.shape[2:]).to(dtype=dt, device=device)
+        # one encode over the 5 * S frames (in runs of whole stories past VAE_PIXELS_PER_CALL)
+        dists = [self.vae.encode(x).latent_dist for x in self._vae_chunks(src)]
+        per_story = all(hasattr(d, "mean") and hasattr(d, "std") for d in dists)
+        if per_story:
+            mean, std = torch.cat([d.mean for d in dists]), torch.cat([d.std for d in dists])
+        need_noise = hasattr(self.scheduler, "sigma_table") and bool(getattr(self.scheduler, "noise_needed", False))
+        T = int(num_inference_steps)
+        if need_noise:
+            self.scheduler.set_timesteps(T, device=None)
+            T = len(self.scheduler.timesteps)
+        z, lat, ctx, masks, noise = [], [], [], [], []
+        for s in range(S):
+            g = gens[s]
+            # the draws of the single-story call, in its order: posterior noise, initial latents, the per-step noise
+            if per_story:
+                m, sd = mean[s * f:(s + 1) * f], std[s * f:(s + 1) * f]
+                z.append(m + sd * torch.randn(m.shape, generator=g, device=m.device, dtype=m.dtype))
+            else:
+                z.append(self.vae.encode(src[s * f:(s + 1) * f]).latent_dist.sample(generator=g))
+            lat.append(self.prepare_latents(1, 4, f, height, width, dt, device, g, None if latents is None
+                                            else latents[s:s + 1]))
+            if need_noise:
+                gdev = g.device if g is not None else device
+                noise.append(torch.stack([torch.randn((1, 4, f, h, w), generator=g, device=gdev, dtype=torch.float32).to(device)
+                                          for _ in range(T)]))
+            label = self.encode_mask(mask_label[s].to(dtype=dt, device=device), 1, cfg_on)
+            text_s = torch.cat([text[(r * S + s) * f:(r * S + s + 1) * f] for r in range(reps)])
+            img1, proj0 = image_embeds_1[s], proj_embeds_0[s]
+            if cfg_on:
+                img1, proj0 = torch.cat([img1] * 2), torch.cat([proj0] * 2)
+            ctx.append(self.build_context(text_s, label, img1, proj0, fix_context_order))
+            masks.append(label)
+        z = torch.stack(z).permute(0, 2, 1, 3, 4) * 0.18215            # (S, 4, 5, h, w)
+        masked_latents = torch.cat([z] * reps)                          # batch row r * S + s
+        mask5 = place_story_rows(masks, reps).view(reps * S, 1, f, h, w)
+        context = place_story_rows(ctx, reps)
+        noise = torch.cat(noise, dim=1) if need_noise else None         # (T, S, 4, 5, h, w)
+        return self._sample_and_decode(torch.cat(lat), mask5, masked_latents, context, dt, num_inference_steps,
+                                       guidance_scale, None, noise, callback, callback_steps, output_type, return_dict,
+                                       png_match)
 
 
 # stage2_batchtest_rcdms_model.py:30 imports RCDMsPipeline but :246 instantiates AnimationPipeline

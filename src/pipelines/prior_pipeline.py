@@ -11,6 +11,7 @@ from typing import Callable, Dict, List, Optional, Union
 import torch
 
 from rcdms_amd.sampler import PriorLoop
+from rcdms_amd.story import check_story_axis, story_count, story_generators
 from src.models.myprior_transformer import MyPriorTransformer
 
 
@@ -117,6 +118,10 @@ class Seq_Inpaint_Prior_Pipeline:
         `callback_on_step_end` is not supported (NotImplementedError)."""
         if callback_on_step_end is not None:
             raise NotImplementedError("per-step callbacks: the sampling loop runs as hipGraph replays")
+        if story_count(prompt, video_length) is not None:
+            return self._call_stories(prompt, imgs_proj_embeds1, mask_label, video_length, num_videos_per_prompt,
+                                      negative_prompt, num_inference_steps, generator, latents, guidance_scale, output_type,
+                                      return_dict)
         if negative_prompt is not None:
             prompt = prompt + negative_prompt
             negative_prompt = 2 * negative_prompt
@@ -151,3 +156,54 @@ class Seq_Inpaint_Prior_Pipeline:
         if not return_dict:
             return (image_embeddings, zero_embeds)
         return KandinskyPriorPipelineOutput(image_embeds=image_embeddings, negative_image_embeds=zero_embeds)
+
+    def _call_stories(self, prompt, imgs_proj_embeds1, mask_label, video_length, num_videos_per_prompt, negative_prompt,
+                      num_inference_steps, generator, latents, guidance_scale, output_type, return_dict):
+        """`prompt` is S lists of `video_length` captions: S stories through one captured loop.  Story s is the single-story
+        call on story s's inputs with story s's generator (one generator: the S calls made one after the other with it) — its
+        initial latents and its (T, 5, E) scheduler noise are drawn per story, in that order.  imgs_proj_embeds1 / mask_label
+        (S, 5, 1, E), latents (S, 5, E) -> image_embeds (S, 5, E)."""
+        S = story_count(prompt, video_length)
+        f = int(video_length)
+        if negative_prompt is not None:
+            raise NotImplementedError("negative_prompt with a story axis: the single-story path doubles its batch for it "
+                                      "(prior_pipeline.py:283-285), which has no per-story meaning")
+        if num_videos_per_prompt != 1:
+            raise NotImplementedError("num_videos_per_prompt != 1 with a story axis")
+        if output_type not in ["pt", "np"]:
+            raise ValueError(f"Only the output types `pt` and `np` are supported not output_type={output_type}")
+        E = self.prior.config.embedding_dim
+        check_story_axis("imgs_proj_embeds1", imgs_proj_embeds1, (S, f, 1, E))
+        check_story_axis("mask_label", mask_label, (S, f, 1, E))
+        if latents is not None:
+            check_story_axis("latents", latents, (S, f, E))
+        gens = story_generators(generator, S)
+        device = self._execution_device
+        self._guidance_scale = guidance_scale
+        flat = [c for story in prompt for c in story]
+        # [uncond: s0 f0..4, s1 f0..4, ...; cond: the same] — the loop's batch rows r * S + s, five frames each
+        emb, hid, mask = self._encode_prompt(flat, device, 1, self.do_classifier_free_guidance, None)
+        T = int(num_inference_steps)
+        lat, noise = [], []
+        for s in range(S):
+            lat.append(self.prepare_latents((f, E), emb.dtype, device, gens[s], None if latents is None else latents[s],
+                                            self.scheduler))
+            noise.append(torch.randn((T, f, E), dtype=torch.float32, device=device, generator=gens[s]))
+        lat, noise = torch.cat(lat), torch.cat(noise, dim=1)
+        proj1 = imgs_proj_embeds1.reshape(S * f, 1, E)
+        label = mask_label.reshape(S * f, 1, E)
+        if self.do_classifier_free_guidance:
+            proj1, label = torch.cat([proj1] * 2), torch.cat([label] * 2)
+        key = (f, hid.shape[1], float(guidance_scale), T, S)
+        if key not in self._loops:
+            self._loops[key] = PriorLoop(self.prior, f, hid.shape[1], guidance_scale, self.scheduler, T, stories=S)
+        loop = self._loops[key]
+        self._num_timesteps = loop.T
+        loop.load(lat / self.scheduler.init_noise_sigma, emb, hid, proj1, label, mask, noise=noise)
+        out = self.prior.post_process_latents(loop.run().clone().to(emb.dtype)).reshape(S, f, E)
+        zero = self.get_zero_embed(S * f, device=out.device).reshape(S, f, -1)
+        if output_type == "np":
+            out, zero = out.cpu().numpy(), zero.cpu().numpy()
+        if not return_dict:
+            return (out, zero)
+        return KandinskyPriorPipelineOutput(image_embeds=out, negative_image_embeds=zero)
