@@ -462,6 +462,13 @@ int rcdm_ff_fused(const rcdm_ff_desc* d, const void* x, const float* ln_gamma, c
  *                  residual add of Transformer3DModel / TemporalTransformer3DModel.forward (attention.py:352-363,
  *                  motion_module.py:170-176) ride too; the feed-forward's output rows are NOT stored (tok keeps the rows
  *                  stage A wrote).  Needs res, no pe.  W_z = fp32 [C][C], passed to rcdm_pack_rowchain as wt.
+ *     tail 4:      out[m][0 : C] = temporal self-attention of q | k | v = y[m][:] W_t^T (W_t as for tail 3; q, k, v rounded to
+ *                  f16 as tail 3 stores them, never stored): for the pixel of row m, softmax over its `frames` rows of
+ *                  q k^T / sqrt(C / 8) per head (8 heads), times v — what rcdm_temporal_attn computes from tail 3's output
+ *                  (motion_module.py:299-302).  Rows are [sample][frame][pixel]: frames = 5, rows_per_frame % 16 == 0 and
+ *                  M % (5 * rows_per_frame) == 0 (RCDM_ESHAPE otherwise), both given with or without pe.  A block takes
+ *                  2 x 16 pixels x 5 frames; with gn_stat, gn_rows == rows_per_frame (one GroupNorm sample per image, any
+ *                  multiple of 16).  out may alias a_in.  The stream is packed for this tail (rcdm_pack_rowchain tail 4).
  *   replaces, in BasicTransformerBlock.forward / Transformer3DModel.forward (attention.py:330,479-514) and
  *   TemporalTransformer3DModel / TemporalTransformerBlock.forward (motion_module.py:166,234-243,299-302):
  *     proj_in -> norm1 -> [to_q | to_k | to_v]                         (res = NULL, tail 3)
@@ -484,8 +491,9 @@ int rcdm_ff_fused(const rcdm_ff_desc* d, const void* x, const float* ln_gamma, c
 typedef struct {
   int32_t M, C;
   int32_t lda, ldr, ldt, ldo;      /* row strides in elements, multiples of 8 (ldr only with res) */
-  int32_t tail;                    /* 0 = feed-forward, 1 = GEMM to C columns, 2 = feed-forward + projection, 3 = GEMM to 3C */
-  int32_t rows_per_frame, frames;  /* only with pe */
+  int32_t tail;                    /* 0 = feed-forward, 1 = GEMM to C columns, 2 = feed-forward + projection, 3 = GEMM to 3C,
+                                      4 = GEMM to 3C + temporal attention */
+  int32_t rows_per_frame, frames;  /* only with pe or tail 4 */
   float eps;                       /* LayerNorm eps (1e-5) */
   int32_t gn_groups, gn_rows;      /* only with gn_stat: groups and rows per sample of the GroupNorm */
   int32_t ldz;                     /* row stride of z_res (tail 2) */
@@ -493,7 +501,7 @@ typedef struct {
 int rcdm_rowchain_supported(int32_t C);
 int rcdm_rowchain_config_supported(int32_t C, int32_t tail, int32_t pe_frames);   /* pe_frames = 0: no pe */
 size_t rcdm_rowchain_stream_bytes(int32_t C, int32_t tail);
-/* wa [C][C]; tail 1 / 3: wt [tail*C][C]; tail 0 / 2: w1 [8C][C], b1 [8C], w2 [C][4C] and b1_packed [8C] (out); tail 2: wt [C][C] */
+/* wa [C][C]; tail 1 / 3: wt [tail*C][C]; tail 4: wt [3C][C]; tail 0 / 2: w1 [8C][C], b1 [8C], w2 [C][4C] and b1_packed [8C] (out); tail 2: wt [C][C] */
 int rcdm_pack_rowchain(const float* wa, int32_t C, int32_t tail, const float* wt, const float* w1, const float* b1,
                        const float* w2, void* wstream, float* b1_packed, void* stream);
 int rcdm_rowchain(const rcdm_rowchain_desc* d, const void* a_in, const void* res, void* tok, const float* a_bias,

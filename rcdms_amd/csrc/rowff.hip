@@ -5,12 +5,14 @@
 //                      out = y W_t^T                      (N = C: cross-attention query, N = 3C: fused q | k | v)
 //                      out = tok + FeedForward_geglu(y)   (y computed with the feed-forward's own LayerNorm)
 //                      out = z_res + (tok + FeedForward_geglu(y)) W_z^T + b_z     (tail 2: the block's proj_out rides too)
+//                      out = temporal self-attention of q | k | v = y W_t^T       (tail 4: q, k, v never leave the CU)
 // Replace, per launch, the chains the library otherwise runs as 3-5 launches with every intermediate tensor in HBM:
 //   * nn.LayerNorm -> diffusers FeedForward(dim, activation_fn="geglu") -> + hidden_states
 //     (BasicTransformerBlock.forward src/models/attention.py:514, TemporalTransformerBlock.forward motion_module.py:243);
 //   * proj_in / to_out[0] (+ residual) -> norm1 / norm2 / norms[i] (+ PositionalEncoding) -> to_q | to_k | to_v
 //     (attention.py:330,482-499,121,139-141; motion_module.py:166,236-241,299-302);
-//   * to_out[0] + residual -> norm3 / ff_norm -> ff -> + residual (attention.py:164,514; motion_module.py:243).
+//   * to_out[0] + residual -> norm3 / ff_norm -> ff -> + residual (attention.py:164,514; motion_module.py:243);
+//   * the q | k | v chain of a motion module and the attention over the frames behind it (motion_module.py:299-302).
 //
 // Decomposition (round 3): the implicit-GEMM kernels tile BOTH dimensions, so their operands
 // stream L2 -> LDS for every tile and every intermediate tensor round-trips HBM.  Here a WAVE owns 16 token rows for the
@@ -48,7 +50,8 @@
 
 namespace {
 
-enum { TAIL_FF = 0, TAIL_N1 = 1, TAIL_FFP = 2, TAIL_N3 = 3 };   // FFP: feed-forward, then a C x C projection (+ bias + residual)
+enum { TAIL_FF = 0, TAIL_N1 = 1, TAIL_FFP = 2, TAIL_N3 = 3, TAIL_ATT = 4 };   // FFP: feed-forward, then a C x C projection (+ bias
+                                                                               // + residual); ATT: q | k | v, then the temporal attention
 
 struct RowArgs {
   const f16* a_in;     // [M][lda]: stage-A input rows (HAS_A), else the rows the LayerNorm reads (and the FF residual)
@@ -71,6 +74,7 @@ struct RowArgs {
   int rows_per_frame, frames;
   int gn_G, gn_rows;    // groups; rows per GroupNorm sample (>= the block's rows: a block meets at most two samples)
   float eps;
+  float att_scale;      // TAIL_ATT: d_head^-1/2
 };
 
 template <int C, int NW, int R, int PD, bool HAS_A, bool A_RES, bool LN_PE, int TAIL>
@@ -82,7 +86,10 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
   constexpr int NG = C / 8;         // feed-forward: groups of 32 hidden units (4C / 32)
   constexpr int NCH_A = HAS_A ? NK : 0;                                   // stage A: NK * NOF fragments
   constexpr bool IS_FF = TAIL == TAIL_FF || TAIL == TAIL_FFP;
-  constexpr int NCH_T = IS_FF ? 3 * NG + (TAIL == TAIL_FFP ? NK : 0) : TAIL * NK;   // FF 3 chunks per group; GEMM NK per C columns
+  // TAIL_ATT takes its rows FRAME-MAJOR (FM): wave w owns frame w % 5 of pixel group 2 * block + w / 5 (16 consecutive pixels of
+  // one (sample, frame) image), so the five frames of a pixel sit in the same lane of five waves of ONE block
+  constexpr bool FM = TAIL == TAIL_ATT;
+  constexpr int NCH_T = IS_FF ? 3 * NG + (TAIL == TAIL_FFP ? NK : 0) : (FM ? 3 : TAIL) * NK;   // FF 3 chunks per group; GEMM NK per C columns
   constexpr int NCH = NCH_A + NCH_T;
   constexpr int NT = NW * 64;
   constexpr int PPW = CHF / NW;     // DMA pieces per wave and chunk
@@ -90,15 +97,30 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
   static_assert(NOF == CHF && CHF % PD == 0 && CHF >= 20 && NOF % 2 == 0, "chunk geometry");
   constexpr int PAR0 = R * CHB;     // parameter region (floats): [a_bias C][gamma C][beta C][pe frames*C][b1p 8C][b2 C | z_bias C]
   constexpr int RS = 2 * C + 16;    // staged output row (bytes)
-  static_assert(NW * 16 * RS <= R * CHB, "epilogue staging exceeds the ring");
+  static_assert(!IS_FF || NW * 16 * RS <= R * CHB, "epilogue staging exceeds the ring");
+  // FM: behind [a_bias][gamma][beta] lies the exchange region X of the attention (one 160-column half of k or v of all NW
+  // waves, XW bytes per wave); until the first k half is written there it holds the prologue's tables (pe, GroupNorm)
+  constexpr int XOFF = PAR0 + 3 * C * 4, XW = (NK / 2) * 1024;
+  static_assert(!FM || (HAS_A && NW == 10 && (5 * C + NW * 2 * C) * 4 <= NW * XW), "frame-major chain geometry");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int l15 = lane & 15, kg = lane >> 4;
-  const int row0 = blockIdx.x * (NW * 16) + wave * 16;
+  int row0_ = blockIdx.x * (NW * 16) + wave * 16, fm_gps = 1, fm_ngrp = 0;
+  bool fm_live = true;
+  const int fm_f = wave % 5;
+  if constexpr (FM) {   // every value here is wave-uniform
+    fm_gps = p.rows_per_frame >> 4;                          // pixel groups per image
+    fm_ngrp = (p.M / (5 * p.rows_per_frame)) * fm_gps;       // and in all
+    const int grp = 2 * blockIdx.x + wave / 5;
+    fm_live = grp < fm_ngrp;   // the last block may own one group only: its other five waves run on group 0's rows, store nothing
+    const int g2 = fm_live ? grp : 0, b = g2 / fm_gps;
+    row0_ = (b * 5 + fm_f) * p.rows_per_frame + 16 * (g2 - b * fm_gps);
+  }
+  const int row0 = row0_;
   const int row = row0 + l15;
-  const bool live = row < p.M;
+  const bool live = FM ? fm_live : row < p.M;
   const int oG = HAS_A ? C : 0, oB = oG + C, oPE = oB + C, oT = oPE + (LN_PE ? p.frames * C : 0);
   const int oZ = oT + (IS_FF ? 8 * C : 0);              // [b2 C][z_bias C] (TAIL_FFP)
   const int oGN = oZ + (TAIL == TAIL_FFP ? 2 * C : 0);  // [2 samples][scale C | shift C] of the prologue GroupNorm
@@ -159,9 +181,25 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
   // GroupNorm apply in the prologue (attention.py:328-330 / motion_module.py:162-166: norm, then proj_in): this block's
   // rows belong to at most two samples; thread (j, c) prepares scale / shift of channel c for the block's sample j
   float gn_sc = 0.f, gn_sh = 0.f;
+  float fm_sc[FM ? 5 : 1], fm_sh[FM ? 5 : 1];
   constexpr bool CAN_GN = HAS_A && !A_RES;
   static_assert(NT == 2 * C, "one thread per (sample slot, channel)");
-  if (CAN_GN && p.gn_stat) {
+  if constexpr (FM && CAN_GN) {
+    // frame-major: every wave has its own sample (gn_rows == rows_per_frame: one per image); slot = wave, five slots per thread
+    if (p.gn_stat) {
+      const int j0 = t >= C ? 1 : 0, ch = t - j0 * C;
+      const float ga = p.gn_g[ch], be = p.gn_b[ch];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        const int j = 2 * i + j0;
+        const int smp = (min(2 * (int)blockIdx.x + j / 5, fm_ngrp - 1) / fm_gps) * 5 + j % 5;
+        const float* st = p.gn_stat + ((size_t)smp * p.gn_G + ch / (C / p.gn_G)) * 2;
+        const float mean = st[0], rstd = st[1];
+        fm_sc[i] = rstd * ga;
+        fm_sh[i] = __builtin_fmaf(-(mean * rstd), ga, be);
+      }
+    }
+  } else if (CAN_GN && p.gn_stat) {
     const int j = t >= C ? 1 : 0, ch = t - j * C;
     const int nsamp = (p.M + p.gn_rows - 1) / p.gn_rows;
     const int smp = min((int)(blockIdx.x * (NW * 16)) / p.gn_rows + j, nsamp - 1);
@@ -179,7 +217,16 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
     if (idx < npar / 4) *(f32x4*)(smem + PAR0 + 16 * idx) = bq[i];
   }
   const float* par = (const float*)(smem + PAR0);
-  if (CAN_GN && p.gn_stat) {
+  if constexpr (FM && CAN_GN) {
+    if (p.gn_stat) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        float* gp = (float*)(smem + PAR0) + oGN + (2 * i + (t >= C ? 1 : 0)) * 2 * C + (t >= C ? t - C : t);
+        gp[0] = fm_sc[i];
+        gp[C] = fm_sh[i];
+      }
+    }
+  } else if (CAN_GN && p.gn_stat) {
     float* gp = (float*)(smem + PAR0) + oGN + (t >= C ? 2 * C : 0) + (t >= C ? t - C : t);
     gp[0] = gn_sc;
     gp[C] = gn_sh;
@@ -190,8 +237,8 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
 
   if (CAN_GN && p.gn_stat) {
     // y = f16(x * scale + shift): the arithmetic of gn_apply_kernel (norm.hip), bit-identical to the separate launch
-    const int j = row0 / p.gn_rows - (int)(blockIdx.x * (NW * 16)) / p.gn_rows;   // wave-uniform: gn_rows % 16 == 0
-    const float* gs = par + oGN + (j > 0 ? 2 * C : 0) + 8 * kg;
+    const int j = FM ? wave : row0 / p.gn_rows - (int)(blockIdx.x * (NW * 16)) / p.gn_rows;   // wave-uniform: gn_rows % 16 == 0
+    const float* gs = par + oGN + (FM ? j * 2 * C : j > 0 ? 2 * C : 0) + 8 * kg;
 #pragma unroll
     for (int s = 0; s < NK; ++s) {
       const f32x4 c0 = *(const f32x4*)(gs + 32 * s), c1 = *(const f32x4*)(gs + 32 * s + 4);
@@ -313,7 +360,7 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
     q += __shfl_xor(q, 16, 64);
     q += __shfl_xor(q, 32, 64);
     const float rstd = rsqrtf(q * (1.0f / C) + p.eps);
-    const float* pep = LN_PE ? par + oPE + (((live ? row : 0) / p.rows_per_frame) % p.frames) * C : par;
+    const float* pep = !LN_PE ? par : FM ? par + oPE + fm_f * C : par + oPE + (((live ? row : 0) / p.rows_per_frame) % p.frames) * C;
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       const int ch = 32 * k + 8 * kg;
@@ -394,7 +441,152 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
     store_pend();
   };
 
-  if constexpr (!IS_FF) {
+  if constexpr (FM) {
+    // ---- q | k | v, then softmax(q k^T * scale) v over the five frames of every pixel (TemporalSelfAttention,
+    // motion_module.py:299-302 -> CrossAttention._attention), as rcdm_temporal_attn computes it from the stored q | k | v.
+    // The stream brings the six 160-column groups as q0 k0 v0 q1 k1 v1 (0 / 1: heads 0-3 / 4-7), so that one half of the
+    // heads is finished while the other half's GEMMs run: a group's f16 results (the bits the tail-3 chain stores) stay in
+    // registers in the operand layout — lane (l15, kg) holds channels 32 m + 8 kg .. + 7 of the half, m < 5 — and k, then
+    // v, of all ten waves pass through X, each wave writing and reading whole lane-linear 1-KiB pieces (conflict-free
+    // b128 accesses).  A piece of 8 channels belongs to head (4 m + kg) / 5: the partial dots of a lane are summed per
+    // head, then over the row's four lanes.  Time line of a half (chunks of its v group, then of the next q group):
+    //   v.0 hand-over: k -> X | v.1-3: 25 partial dots (frame, m) | v.4: cross-lane sums | (next q.0: softmax)
+    //   q.0 hand-over: v -> X | q.1-3: 25 (m, frame) products -> o | k.0 hand-over: o -> memory
+    // Every write of X follows a barrier behind the last read of what it replaces, and is itself followed by a barrier
+    // before its first read (the in-order LDS counter has passed it by then: later fragment reads were waited for).
+    constexpr int HG = NK / 2;
+    char* const X = smem + XOFF;
+    const int kgq = lane16 >> 8, xme = wave * XW + lane16, xgrp = (wave / 5) * 5 * XW + lane16;
+    const bool c1 = kgq == 0, c2 = kgq <= 1, c3 = kgq <= 2;   // piece m = 1 / 2 / 3 belongs to head m - 1 (else to head m)
+    f16x8 qh[HG], pend[HG], oh[HG];
+    f32x4 acc[NOF / 2];
+    float sc[4][5], o8[8];
+    auto round_to = [&](f16x8 (&dst)[HG]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int m = 0; m < HG; ++m)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          dst[m][e] = (f16)acc[2 * m][e];
+          dst[m][4 + e] = (f16)acc[2 * m + 1][e];
+        }
+    };
+    auto xput = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int m = 0; m < HG; ++m) *(f16x8*)(X + xme + m * 1024) = pend[m];
+    };
+    auto xget = [&](int fp, int m) __attribute__((always_inline)) -> f16x8 { return *(const f16x8*)(X + xgrp + fp * XW + m * 1024); };
+    auto score_item = [&](int fp, int m) __attribute__((always_inline)) {
+      const f16x8 kv = xget(fp, m);
+      float d = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; e += 2)   // v_dot2_f32_f16: exact products, fp32 sums; q stays packed (no 40 converted copies)
+        d = __builtin_amdgcn_fdot2(f16x2{qh[m][e], qh[m][e + 1]}, f16x2{kv[e], kv[e + 1]}, d, false);
+      // (the empty asm statements here and below pin each item's arithmetic to its slice, as in the GEGLU slices)
+      if (m == 0) {
+        sc[0][fp] = d; sc[1][fp] = 0.f; sc[2][fp] = 0.f; sc[3][fp] = 0.f;
+        asm volatile("" : "+v"(sc[0][fp]));
+      } else if (m == 4) {
+        sc[3][fp] += d;
+        asm volatile("" : "+v"(sc[3][fp]));
+      } else {
+        const float lo = (m == 1 ? c1 : m == 2 ? c2 : c3) ? d : 0.f;
+        sc[m - 1][fp] += lo;
+        sc[m][fp] += d - lo;
+        asm volatile("" : "+v"(sc[m - 1][fp]), "+v"(sc[m][fp]));
+      }
+    };
+    auto reduce_item = [&](int h, int fp) __attribute__((always_inline)) {
+      float v = sc[h][fp];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      asm volatile("" : "+v"(v));   // the sum here, not sunk to its use with both addends kept alive
+      sc[h][fp] = v;
+    };
+    // the arithmetic of temporal_attn_kernel (attn.hip): scale, max, __expf, sum, p_j = e_j * rcp(sum)
+    auto softmax_head = [&](int h) __attribute__((always_inline)) {
+      float mx = sc[h][0] * p.att_scale;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        sc[h][j] *= p.att_scale;
+        mx = fmaxf(mx, sc[h][j]);
+      }
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        sc[h][j] = __expf(sc[h][j] - mx);
+        sum += sc[h][j];
+      }
+      const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+      for (int j = 0; j < 5; ++j) sc[h][j] *= inv;
+      asm volatile("" : "+v"(sc[h][0]), "+v"(sc[h][1]), "+v"(sc[h][2]), "+v"(sc[h][3]), "+v"(sc[h][4]));
+    };
+    auto pv_item = [&](int m, int fp) __attribute__((always_inline)) {
+      const f16x8 vv = xget(fp, m);
+      const float pj = m == 0 ? sc[0][fp] : m == 4 ? sc[3][fp] : (m == 1 ? c1 : m == 2 ? c2 : c3) ? sc[m - 1][fp] : sc[m][fp];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o8[e] = __builtin_fmaf(pj, (float)vv[e], fp == 0 ? 0.f : o8[e]);
+      if (fp == 4) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) oh[m][e] = (f16)o8[e];
+        asm volatile("" : "+v"(oh[m]));
+      } else {
+        asm volatile("" : "+v"(o8[0]), "+v"(o8[1]), "+v"(o8[2]), "+v"(o8[3]), "+v"(o8[4]), "+v"(o8[5]), "+v"(o8[6]), "+v"(o8[7]));
+      }
+    };
+    auto store_o = [&](int half) __attribute__((always_inline)) {
+      if (live) {
+        f16* op = p.out + (size_t)row * p.ldo + half * (C / 2) + 8 * kgq;
+#pragma unroll
+        for (int m = 0; m < HG; ++m) st16(op + 32 * m, oh[m]);
+      }
+    };
+    // one 160-column group: HH = half, GRP = 0 / 1 / 2 for q / k / v (template constants: what rides in a chunk is decided here)
+    auto group = [&](auto hh_c, auto grp_c) __attribute__((always_inline)) {
+      constexpr int hh = decltype(hh_c)::value, grp = decltype(grp_c)::value;
+#pragma unroll
+      for (int cc = 0; cc < HG; ++cc)
+        run_chunk(
+            [&](int i, f16x8 w) __attribute__((always_inline)) {
+              const int s = 2 * cc + i / (NOF / 2), fi = i % (NOF / 2);
+              acc[fi] = mm(w, xr[s], s == 0 ? z4 : acc[fi]);
+            },
+            [&](int i) __attribute__((always_inline)) {
+              if constexpr (grp == 2) {   // this half's scores, under its v GEMM
+                if (cc >= 1 && cc <= 3 && i < (cc == 3 ? 5 : 10)) score_item(2 * (cc - 1) + i / 5, i % 5);
+                if (cc == 4) reduce_item(i / 5, i % 5);
+              } else if constexpr (grp == 0 && hh == 1) {   // the first half's softmax and output, under the second half's q GEMM
+                if (cc == 0 && i % 5 == 2) softmax_head(i / 5);
+                if (cc >= 1 && cc <= 3 && i < (cc == 3 ? 5 : 10)) pv_item(2 * (cc - 1) + i / 5, i % 5);
+              }
+            },
+            [&]() __attribute__((always_inline)) {
+              if (cc == 0 && (grp == 2 || (grp == 0 && hh == 1))) xput();
+              if (cc == 0 && grp == 1 && hh == 1) store_o(0);
+            });
+      if constexpr (grp == 0) round_to(qh); else round_to(pend);
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    group(I0{}, I0{}); group(I0{}, I1{}); group(I0{}, I2{});
+    group(I1{}, I0{}); group(I1{}, I1{}); group(I1{}, I2{});
+    // the second half's v: the stream has ended, nothing is left to hide under
+#pragma unroll
+    for (int h = 0; h < 4; ++h) softmax_head(h);
+    wait_lgkm0();
+    wait_vm<0>();    // the zero-fill pieces issued past the end of the stream (and the stores so far)
+    tick_barrier();  // every wave is done reading k
+    xput();
+    wait_lgkm0();
+    tick_barrier();
+#pragma unroll
+    for (int m = 0; m < HG; ++m)
+#pragma unroll
+      for (int fp = 0; fp < 5; ++fp) pv_item(m, fp);
+    store_o(1);
+    return;
+  } else if constexpr (!IS_FF) {
     gemm_groups(std::integral_constant<int, 2 * TAIL>{}, std::false_type{});
     return;
   } else {
@@ -567,14 +759,22 @@ __global__ __launch_bounds__(NW * 64) void row_chain_kernel(const RowArgs p) {
 // N = C GEMM blocks in the P layout (stage A, tail GEMM): n_blocks blocks of C output channels; fragment order per block:
 // half (NOF / 2 fragments), k-step, fragment.  Fragment i of a block, D row r  <->  channel 32 (i >> 1) + 8 (r >> 2) +
 // 4 (i & 1) + (r & 3) of the block.
-__global__ void pack_pgemm_kernel(const float* __restrict__ w, int C, int n_blocks, f16* __restrict__ ws) {
+// by_half (n_blocks = 3, TAIL_ATT): the six 160-column groups leave in the order q0 k0 v0 q1 k1 v1 instead of q0 q1 k0 k1 v0 v1.
+__global__ void pack_pgemm_kernel(const float* __restrict__ w, int C, int n_blocks, f16* __restrict__ ws, int by_half) {
   const int NK = C / 32, NOF = C / 16, HF = NOF / 2;
   const size_t per_block = (size_t)NOF * NK * 512, total = per_block * n_blocks;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int j = (int)(idx & 7), L = (int)((idx >> 3) & 63);
     const size_t fq = idx >> 9;
-    const int blk = (int)(fq / (NOF * NK)), f = (int)(fq % (NOF * NK));
-    const int h = f / (HF * NK), rem = f % (HF * NK), s = rem / HF, fi = rem % HF;
+    int blk = (int)(fq / (NOF * NK));
+    const int f = (int)(fq % (NOF * NK));
+    int h = f / (HF * NK);
+    const int rem = f % (HF * NK), s = rem / HF, fi = rem % HF;
+    if (by_half) {
+      const int gs = 2 * blk + h;   // group of the stream -> (matrix, half)
+      blk = gs % 3;
+      h = gs / 3;
+    }
     const int i = h * HF + fi, r = L & 15, kq = L >> 4;
     const int n = blk * C + 32 * (i >> 1) + 8 * (r >> 2) + 4 * (i & 1) + (r & 3);
     ws[idx] = (f16)w[(size_t)n * C + 32 * s + 8 * kq + j];
@@ -625,11 +825,12 @@ __global__ void pack_ff_stream_kernel(const float* __restrict__ w1, const float*
 
 template <bool HAS_A, bool A_RES, bool LN_PE, int TAIL>
 int launch_chain(const RowArgs& a, hipStream_t stream) {
-  constexpr int C = 320, NW = 10, R = 7, PD = 2;
+  constexpr int C = 320, NW = 10, PD = 2;
+  constexpr int R = TAIL == TAIL_ATT ? 5 : 7;   // the attention's exchange region takes two chunks' worth of LDS from the ring
   constexpr int CHB = 2 * (C / 32) * 1024;
   const int npar = (HAS_A ? C : 0) + 2 * C + (LN_PE ? a.frames * C : 0) + (TAIL == TAIL_FF || TAIL == TAIL_FFP ? 8 * C : 0) +
                    (TAIL == TAIL_FFP ? 2 * C : 0);
-  const int lds = R * CHB + (npar + (a.gn_stat ? 4 * C : 0)) * 4;
+  const int lds = TAIL == TAIL_ATT ? R * CHB + 3 * C * 4 + NW * (C / 64) * 1024 : R * CHB + (npar + (a.gn_stat ? 4 * C : 0)) * 4;
   if (lds > 160 * 1024) return RCDM_ESHAPE;
   static bool attr_set[64] = {};
   if (rcdm_first_on_device(attr_set) &&
@@ -662,8 +863,9 @@ int rcdm_rowchain_supported(int32_t C) { return C == 320 ? 1 : 0; }
 // pe).  pe rides with tail 1 / 3 only (with the feed-forward tails the parameter region would not fit the 160 KB of LDS)
 // and for at most 8 frames.
 int rcdm_rowchain_config_supported(int32_t C, int32_t tail, int32_t pe_frames) {
-  if (C != 320 || tail < 0 || tail > 3) return 0;
+  if (C != 320 || tail < 0 || tail > 4) return 0;
   if (pe_frames < 0 || pe_frames > 8) return 0;
+  if (tail == 4 && pe_frames != 0 && pe_frames != 5) return 0;   // the attention tail: five frames (a block = 2 x 5 waves)
   if (pe_frames > 0 && (tail == 0 || tail == 2)) return 0;
   return 1;
 }
@@ -671,8 +873,8 @@ int rcdm_rowchain_config_supported(int32_t C, int32_t tail, int32_t pe_frames) {
 size_t rcdm_ff_stream_bytes(int32_t C) { return C > 0 ? (size_t)24 * C * C : 0; }
 
 size_t rcdm_rowchain_stream_bytes(int32_t C, int32_t tail) {
-  if (C <= 0 || tail < 0 || tail > 3) return 0;
-  return (size_t)2 * C * C * (1 + (tail == 0 ? 12 : tail == 2 ? 13 : tail));
+  if (C <= 0 || tail < 0 || tail > 4) return 0;
+  return (size_t)2 * C * C * (1 + (tail == 0 ? 12 : tail == 2 ? 13 : tail == 4 ? 3 : tail));
 }
 
 int rcdm_pack_ff_stream(const float* w1, const float* b1, const float* w2, int32_t C, void* wstream, float* b1_packed,
@@ -687,20 +889,21 @@ int rcdm_pack_ff_stream(const float* w1, const float* b1, const float* w2, int32
 int rcdm_pack_rowchain(const float* wa, int32_t C, int32_t tail, const float* wt, const float* w1, const float* b1,
                        const float* w2, void* wstream, float* b1_packed, void* stream) {
   if (!wa || !wstream || C <= 0) return RCDM_EINVAL;
-  if (C % 32 || tail < 0 || tail > 3) return RCDM_ESHAPE;
+  if (C % 32 || tail < 0 || tail > 4) return RCDM_ESHAPE;
   const bool ff = tail == 0 || tail == 2;
   if ((ff && (!w1 || !b1 || !w2 || !b1_packed)) || (tail != 0 && !wt)) return RCDM_EINVAL;
   f16* ws = (f16*)wstream;
-  hipLaunchKernelGGL(pack_pgemm_kernel, dim3(grid_for((size_t)C * C)), dim3(256), 0, (hipStream_t)stream, wa, C, 1, ws);
+  hipLaunchKernelGGL(pack_pgemm_kernel, dim3(grid_for((size_t)C * C)), dim3(256), 0, (hipStream_t)stream, wa, C, 1, ws, 0);
   ws += (size_t)C * C;
   if (ff) {
     hipLaunchKernelGGL(pack_ff_stream_kernel, dim3(grid_for((size_t)12 * C * C)), dim3(256), 0, (hipStream_t)stream, w1, b1, w2, C,
                        ws, b1_packed, tail == 2 ? 1 : 0);
     ws += (size_t)12 * C * C;
   }
+  const int nt = ff ? 1 : tail == 4 ? 3 : tail;
   if (tail != 0)   // tail 2: wt = the trailing [C][C] projection
-    hipLaunchKernelGGL(pack_pgemm_kernel, dim3(grid_for((size_t)(ff ? 1 : tail) * C * C)), dim3(256), 0, (hipStream_t)stream, wt, C,
-                       ff ? 1 : tail, ws);
+    hipLaunchKernelGGL(pack_pgemm_kernel, dim3(grid_for((size_t)nt * C * C)), dim3(256), 0, (hipStream_t)stream, wt, C, nt, ws,
+                       tail == 4 ? 1 : 0);
   return rcdm_check_launch();
 }
 
@@ -725,12 +928,16 @@ int rcdm_rowchain(const rcdm_rowchain_desc* d, const void* a_in, const void* res
                   const float* b2, void* out, const float* gn_stat, const float* gn_gamma, const float* gn_beta,
                   const void* z_res, const float* z_bias, void* stream) {
   if (!d || !a_in || !tok || !a_bias || !ln_gamma || !ln_beta || !wstream || !out) return RCDM_EINVAL;
-  const int ncol = d->tail == 0 || d->tail == 2 ? d->C : d->tail * d->C;
+  const int ncol = d->tail == 0 || d->tail == 2 || d->tail == 4 ? d->C : d->tail * d->C;
   if (d->M <= 0 || d->lda < d->C || d->ldt < d->C || d->ldo < ncol || ((d->lda | d->ldt | d->ldo) & 7)) return RCDM_EINVAL;
   if (res && (d->ldr < d->C || (d->ldr & 7))) return RCDM_EINVAL;
   if (pe && (d->rows_per_frame <= 0 || d->frames <= 0 || d->frames > 8)) return RCDM_EINVAL;
   if ((d->tail == 0 || d->tail == 2) && (!b1_packed || !b2)) return RCDM_EINVAL;
-  if (d->C != 320 || d->tail < 0 || d->tail > 3) return RCDM_ESHAPE;
+  if (d->C != 320 || d->tail < 0 || d->tail > 4) return RCDM_ESHAPE;
+  if (d->tail == 4) {   // frame-major blocks: whole samples of five frames, images of whole 16-pixel groups
+    if (d->rows_per_frame <= 0 || d->frames <= 0) return RCDM_EINVAL;
+    if (d->frames != 5 || d->rows_per_frame % 16 || d->M % (5 * d->rows_per_frame)) return RCDM_ESHAPE;
+  }
   if (!rcdm_rowchain_config_supported(d->C, d->tail, pe ? d->frames : 0)) return RCDM_ESHAPE;
   if (misaligned16(a_bias) || misaligned16(ln_gamma) || misaligned16(ln_beta) || misaligned16(pe) || misaligned16(b1_packed) ||
       misaligned16(b2) || misaligned16(z_bias) || misaligned16(gn_gamma) || misaligned16(gn_beta) || misaligned16(a_in) ||
@@ -744,13 +951,15 @@ int rcdm_rowchain(const rcdm_rowchain_desc* d, const void* a_in, const void* res
   }
   if (gn_stat) {   // GroupNorm apply on the incoming rows: only the form without a stage-A residual has the operand free
     if (res || !gn_gamma || !gn_beta || d->gn_groups <= 0 || d->gn_rows <= 0) return RCDM_EINVAL;
-    if (d->C % d->gn_groups || d->gn_rows % 16 || d->gn_rows < 160) return RCDM_ESHAPE;
+    if (d->C % d->gn_groups || d->gn_rows % 16) return RCDM_ESHAPE;
+    if (d->tail == 4 ? d->gn_rows != d->rows_per_frame : d->gn_rows < 160) return RCDM_ESHAPE;
   }
   RowArgs a{};
   a.a_in = (const f16*)a_in; a.res = (const f16*)res; a.tok = (f16*)tok; a.out = (f16*)out; a.wstream = (const f16*)wstream;
   a.a_bias = a_bias; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.pe = pe; a.b1p = b1_packed; a.b2 = b2;
   a.M = d->M; a.lda = d->lda; a.ldr = d->ldr; a.ldt = d->ldt; a.ldo = d->ldo;
-  a.rows_per_frame = pe ? d->rows_per_frame : 1; a.frames = pe ? d->frames : 1; a.eps = d->eps;
+  a.rows_per_frame = pe || d->tail == 4 ? d->rows_per_frame : 1; a.frames = pe || d->tail == 4 ? d->frames : 1; a.eps = d->eps;
+  a.att_scale = (float)(1.0 / sqrt((double)(d->C / 8)));   // eight heads (d_head = 40 at C = 320)
   a.z_res = (const f16*)z_res; a.z_bias = z_bias; a.ldz = d->ldz;
   a.gn_stat = gn_stat; a.gn_g = gn_gamma; a.gn_b = gn_beta; a.gn_G = d->gn_groups; a.gn_rows = d->gn_rows;
   hipStream_t s = (hipStream_t)stream;
@@ -761,7 +970,8 @@ int rcdm_rowchain(const rcdm_rowchain_desc* d, const void* a_in, const void* res
     case 0: return RCDM_CHAIN(TAIL_FF);
     case 1: return RCDM_CHAIN(TAIL_N1);
     case 2: return launch_chain<true, true, false, TAIL_FFP>(a, s);
-    default: return RCDM_CHAIN(TAIL_N3);
+    case 3: return RCDM_CHAIN(TAIL_N3);
+    default: return RCDM_CHAIN(TAIL_ATT);
   }
 #undef RCDM_CHAIN
 }

@@ -121,6 +121,10 @@ class _ChainMinRows:
 
 
 CHAIN_MIN_ROWS = _ChainMinRows()
+# rows from which the q | k | v chains of a motion module carry their temporal attention (tail 4): the same rule, held on its
+# own — the form is measured at a chip's worth of blocks only, and a chain threshold lowered for a small geometry keeps the
+# two-launch form there
+MOTION_FUSE_MIN_ROWS = _ChainMinRows()
 
 
 def emit_rowchain(plan, a_in, res, tok, a_bias, ln, pe, stream, tail, out, rows_per_frame=1, frames=1, b2=None, gn=None,
@@ -128,7 +132,8 @@ def emit_rowchain(plan, a_in, res, tok, a_bias, ln, pe, stream, tail, out, rows_
     """tok = a_in W_a^T + a_bias (+ res);  y = LayerNorm(tok) (+ pe);  tail 1 / 3: out = y W_t^T;  tail 0: out = tok + FF(y).
     ln = (gamma, beta); stream = Packer.chain(...); gn = emit_groupnorm_stats(...): a_in is the RAW input of that
     GroupNorm and the kernel applies it while loading its rows (res must be None).  tail 2, z = (z_res rows, z_bias):
-    out = z_res + (tok + FF(y)) W_z^T + z_bias, the feed-forward's own output rows are not stored."""
+    out = z_res + (tok + FF(y)) W_z^T + z_bias, the feed-forward's own output rows are not stored.  tail 4 (rows_per_frame,
+    frames = 5, eight heads): out = the temporal self-attention of the q | k | v that tail 3 would store, [M][C]."""
     ws, b1p = stream
     M, C = a_in.M, a_in.C
     assert_no_pending_gn(plan, "a row-chain launch")
@@ -422,10 +427,16 @@ def emit_motion(plan, w, x, geo, heads, out, groups=32, prior_state=False, out_g
         qkv = plan.rows("qkv", g.M, 3 * C)
         ao = plan.rows("attn_out", g.M, C)
         a0, a1 = w.attn
-        emit_rowchain(plan, x if gn else a, None, tok, w.proj_in_b, (a0.ln_g, a0.ln_b), a0.pe, w.chains[0], 3, qkv, g.hw, g.f, gn=gn)
-        emit_temporal_attn(plan, qkv, g.b, g.f, g.hw, heads, d_head, ao)
-        emit_rowchain(plan, ao, tok, tok, a0.o_b, (a1.ln_g, a1.ln_b), a1.pe, w.chains[1], 3, qkv, g.hw, g.f)
-        emit_temporal_attn(plan, qkv, g.b, g.f, g.hw, heads, d_head, ao)
+        if (w.chains_att is not None and g.f == 5 and heads == 8 and g.hw % 16 == 0 and g.M >= MOTION_FUSE_MIN_ROWS and
+                hip.rowchain_config_supported(C, 4, g.f)):
+            # the attention rides in the chain launches (frame-major blocks): q | k | v never leave the CU
+            emit_rowchain(plan, x if gn else a, None, tok, w.proj_in_b, (a0.ln_g, a0.ln_b), a0.pe, w.chains_att[0], 4, ao, g.hw, g.f, gn=gn)
+            emit_rowchain(plan, ao, tok, tok, a0.o_b, (a1.ln_g, a1.ln_b), a1.pe, w.chains_att[1], 4, ao, g.hw, g.f)
+        else:
+            emit_rowchain(plan, x if gn else a, None, tok, w.proj_in_b, (a0.ln_g, a0.ln_b), a0.pe, w.chains[0], 3, qkv, g.hw, g.f, gn=gn)
+            emit_temporal_attn(plan, qkv, g.b, g.f, g.hw, heads, d_head, ao)
+            emit_rowchain(plan, ao, tok, tok, a0.o_b, (a1.ln_g, a1.ln_b), a1.pe, w.chains[1], 3, qkv, g.hw, g.f)
+            emit_temporal_attn(plan, qkv, g.b, g.f, g.hw, heads, d_head, ao)
         if w.chain_ffz is not None:
             emit_rowchain(plan, ao, tok, tok, a1.o_b, w.ff_ln, None, w.chain_ffz, 2, out, b2=w.ff2_b, z=(x, w.proj_out_b))
             return

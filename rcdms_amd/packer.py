@@ -154,7 +154,7 @@ class Packer:
 
     def chain(self, wa_key, tail, wt_keys=(), ff_keys=None):
         """(weight stream, packed b1 | None) for rcdm_rowchain: stage-A matrix wa_key [C][C] (a Linear or 1x1 conv weight),
-        then tail 1 / 3: the stacked [tail*C][C] matrices wt_keys, tail 0: the feed-forward (w1, b1, w2) keys, tail 2: the
+        then tail 1 / 3 / 4: the stacked [tail*C][C] ([3C][C] for tail 4) matrices wt_keys, tail 0: the feed-forward (w1, b1, w2) keys, tail 2: the
         feed-forward keys and wt_keys = (the trailing [C][C] projection,) whose bias the launch takes separately.  None
         when the library has no chain kernel for this width or a tail 1 / 3 projection carries a bias."""
         if not SW.ROW_CHAIN or any(not self.has(k) for k in (wa_key, *wt_keys, *(ff_keys or ()))):
@@ -179,7 +179,7 @@ class Packer:
             return ws, b1p
         if tail:
             wt = torch.cat([self.f32(k) for k in wt_keys], dim=0).contiguous()
-            if tuple(wt.shape) != (tail * Cc, Cc):
+            if tuple(wt.shape) != ((3 if tail == 4 else tail) * Cc, Cc):
                 return None
             hip.pack_rowchain(wa.data_ptr(), Cc, tail, wt.data_ptr(), 0, 0, 0, ws.data_ptr(), 0)
             self._tmp += [wa, wt]
@@ -362,7 +362,7 @@ def pack_motion(pk, p, n_attn, lnx=True):
     w.ffz = pk.ffz(b + "ff.net.2.weight", b + "ff.net.2.bias", p + "proj_out.weight", p + "proj_out.bias") if lnx else None
     # row-stationary chains: proj_in -> norms[0] + pe -> qkv;  to_out + res -> norms[1] + pe -> qkv;  to_out + res ->
     # ff_norm -> ff -> + res
-    w.chains = w.chain_ffz = None
+    w.chains = w.chain_ffz = w.chains_att = None
     if n_attn == 2:
         a0, a1 = b + "attention_blocks.0.", b + "attention_blocks.1."
         qkv = lambda a: (a + "to_q.weight", a + "to_k.weight", a + "to_v.weight")
@@ -371,6 +371,9 @@ def pack_motion(pk, p, n_attn, lnx=True):
                        ff_keys=(b + "ff.net.0.proj.weight", b + "ff.net.0.proj.bias", b + "ff.net.2.weight"))]
         if all(c is not None for c in ch) and all(at.pe is not None for at in w.attn):
             w.chains = ch
+            # the same two q | k | v chains with the temporal attention as their tail (their stream in half-of-the-heads order)
+            if SW.MOTION_FUSE and hip.rowchain_config_supported(C, 4, 5):
+                w.chains_att = [pk.chain(p + "proj_in.weight", 4, wt_keys=qkv(a0)), pk.chain(a0 + "to_out.0.weight", 4, wt_keys=qkv(a1))]
             # proj_out + the module's residual behind the feed-forward (zero-initialised proj_out included)
             w.chain_ffz = pk.chain(a1 + "to_out.0.weight", 2, wt_keys=(p + "proj_out.weight",),
                                    ff_keys=(b + "ff.net.0.proj.weight", b + "ff.net.0.proj.bias", b + "ff.net.2.weight"))

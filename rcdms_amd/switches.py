@@ -17,6 +17,7 @@ LNX = _on("RCDM_LNX")                # 0: stand-alone LayerNorm launches below t
 FFZ = _on("RCDM_FFZ")                # 0: ff.net.2 and proj_out as two GEMMs instead of the composed K = 5C one (attention.py:361,514)
 FF_FUSE = _on("RCDM_FF_FUSE")        # 0: LayerNorm -> GEGLU -> ff.net.2 as three launches instead of rcdm_ff_fused
 ROW_CHAIN = _on("RCDM_ROWCHAIN")     # 0: separate launches instead of the row-stationary chains of the 64x64 level
+MOTION_FUSE = _on("RCDM_MOTION_FUSE")  # 0: q | k | v to memory + rcdm_temporal_attn instead of the attention inside the 64x64 level's chain launches (motion_module.py:299-302)
 RANK1_CTX = _on("RCDM_RANK1_CTX")    # 0: cross-attention evaluated in full even for images whose context rows are all equal
 # which latent sizes run the stride-1 3x3 convolutions of their ResNet blocks (>= 640 channels) in the Winograd F(2x2, 3x3) form
 # (rcdm_conv3x3_wino, with the GroupNorm apply + SiLU in its input transform) instead of the nine-tap implicit GEMM
@@ -46,6 +47,6 @@ CHAIN_MIN_ROWS = os.environ.get("RCDM_CHAIN_MIN_ROWS")   # token rows from which
 
 TABLE = {
     "RCDM_SC_FOLD": SC_FOLD, "RCDM_UP2": UP2, "RCDM_GN_PRESTAT": GN_PRESTAT, "RCDM_LNX": LNX, "RCDM_FFZ": FFZ,
-    "RCDM_FF_FUSE": FF_FUSE, "RCDM_ROWCHAIN": ROW_CHAIN, "RCDM_RANK1_CTX": RANK1_CTX, "RCDM_WINO": _w, "RCDM_WINO_MIN_C": WINO_MIN_C, "RCDM_UP9": UP9, "RCDM_OUT_TAPS": OUT_TAPS, "RCDM_CHAIN_MIN_ROWS": CHAIN_MIN_ROWS,
+    "RCDM_FF_FUSE": FF_FUSE, "RCDM_ROWCHAIN": ROW_CHAIN, "RCDM_MOTION_FUSE": MOTION_FUSE, "RCDM_RANK1_CTX": RANK1_CTX, "RCDM_WINO": _w, "RCDM_WINO_MIN_C": WINO_MIN_C, "RCDM_UP9": UP9, "RCDM_OUT_TAPS": OUT_TAPS, "RCDM_CHAIN_MIN_ROWS": CHAIN_MIN_ROWS,
     "RCDM_VAE_FLASH": VAE_FLASH,
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Micro-benchmark of single librcdm_hip kernels at the UNet's hot shapes (HIP-event timed, interleaved rounds).
-usage: python tools/kbench.py [gemm|conv|attn|norm|ff|chain|ladder|all] [--variants 0,1,2] [--rounds 5]"""
+usage: python tools/kbench.py [gemm|conv|attn|norm|ff|chain|motion|ladder|all] [--variants 0,1,2] [--rounds 5]"""
 import argparse
 import os
 import sys
@@ -346,6 +346,46 @@ def bench_chain(rounds, only=""):
                   f"stats + rcdm_rowchain {medg2:7.1f}us (min {mng2:.1f}) {fl / medg2 / 1e6:6.0f}TF", flush=True)
 
 
+def bench_motion(rounds):
+    """One attention of a 64x64-level motion module (M = 40960, five frames): to_out + res -> LN + pe -> q | k | v, then the
+    temporal attention — rcdm_rowchain tail 3 + rcdm_temporal_attn against rcdm_rowchain tail 4 (the attention as the chain's
+    tail), and the tail-3 chain alone."""
+    M, C, hw = 40960, 320, 4096
+    a = torch.randn(M, C, device=DEV).half()
+    tok = torch.randn(M, C, device=DEV).half()
+    wa = torch.randn(C, C, device=DEV) * C ** -0.5
+    ba, g, b = torch.randn(C, device=DEV), torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+    pe = torch.randn(5, C, device=DEV)
+    wt = torch.randn(3 * C, C, device=DEV) * C ** -0.5
+    qkv = torch.empty(M, 3 * C, device=DEV, dtype=torch.float16)
+    ao = torch.empty(M, C, device=DEV, dtype=torch.float16)
+    ws3 = torch.empty(hip.rowchain_stream_bytes(C, 3), dtype=torch.uint8, device=DEV)
+    ws4 = torch.empty(hip.rowchain_stream_bytes(C, 4), dtype=torch.uint8, device=DEV)
+    hip.pack_rowchain(wa.data_ptr(), C, 3, wt.data_ptr(), 0, 0, 0, ws3.data_ptr(), 0)
+    hip.pack_rowchain(wa.data_ptr(), C, 4, wt.data_ptr(), 0, 0, 0, ws4.data_ptr(), 0)
+    d3 = hip.RowChainDesc(M, C, C, C, C, 3 * C, 3, hw, 5, 1e-5)
+    d4 = hip.RowChainDesc(M, C, C, C, C, C, 4, hw, 5, 1e-5)
+    td = hip.TemporalAttnDesc(M // (5 * hw), 5, hw, 8, 40, 3 * C, C, 40 ** -0.5)
+
+    def chain3():
+        hip.rowchain(d3, a.data_ptr(), tok.data_ptr(), tok.data_ptr(), ba.data_ptr(), g.data_ptr(), b.data_ptr(), pe.data_ptr(),
+                     ws3.data_ptr(), 0, 0, qkv.data_ptr())
+
+    def two():
+        chain3()
+        hip.temporal_attn(td, qkv.data_ptr(), ao.data_ptr())
+
+    def fused():
+        hip.rowchain(d4, a.data_ptr(), tok.data_ptr(), tok.data_ptr(), ba.data_ptr(), g.data_ptr(), b.data_ptr(), pe.data_ptr(),
+                     ws4.data_ptr(), 0, 0, ao.data_ptr())
+    for r in range(3):   # interleaved
+        m3, _ = timeit(chain3, rounds)
+        m2, n2 = timeit(two, rounds)
+        m4, n4 = timeit(fused, rounds)
+        print(f"motion attention M={M}: tail-3 chain {m3:6.1f}us | + temporal_attn {m2:6.1f}us (min {n2:.1f}) | tail-4 chain {m4:6.1f}us "
+              f"(min {n4:.1f})", flush=True)
+
+
 def bench_ladder(rounds):
     """The guide's yardstick (cdna_hip_programming.md, "optimization ladder at 4096^3": 874 TFLOP/s for the 128x128 two-barrier
     structure, ~1330 for the 256x256 8-phase + swizzle template, uniform random operands): rcdm_gemm at M = N = K = 4096 (and
@@ -405,5 +445,7 @@ if __name__ == "__main__":
         bench_ff(a.rounds, a.only)
     if a.what in ("chain", "all"):
         bench_chain(a.rounds, a.only)
+    if a.what in ("motion", "all"):
+        bench_motion(a.rounds)
     if a.what == "ladder":
         bench_ladder(a.rounds)
