@@ -596,6 +596,38 @@ int rcdm_cfg_pndm_step(const void* eps, int32_t ld, float* latents, float* histo
 int rcdm_cfg_sigma_step(const void* eps, int32_t ld, float* latents, float* model_in, float* history, const float* noise,
                         int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W, float guidance_scale,
                         const float* table, const int32_t* step_counter, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Guidance rescale (Lin et al. 2023 §3.4, diffusers `rescale_noise_cfg`; the `guidance_rescale` argument the reference
+ *   driver passes, stage2_batchtest_rcdms_model.py:352) inside the captured step.  Per story s, over its n = 4 f H W
+ *   elements, with e = eps_u + g (eps_c - eps_u) in fp32 from the f16 eps rows:
+ *     factor[s] = phi std(eps_c) / std(e) + (1 - phi)          std unbiased (n - 1), as torch.std
+ *   and the step then uses factor[s] e wherever it used e (x0, the multistep history, d of the table form).
+ *   A deliberate guard: std(e) == 0 (a constant prediction) gives factor 1 where diffusers divides and hands on inf / nan.
+ * rcdm_cfg_rescale_factor: two launches — fixed-order per-block partial sums, shifted by the story's first element, into
+ *   `workspace`; then one thread per story adds them in block order in fp64 — so the factors are bitwise reproducible; no
+ *   atomics, no counters, and nothing is read from `workspace` that this call did not write (no initialisation needed).
+ *   eps as the step kernels take it: f16 rows [(2S)*f*H*W][ld], uncond block first, channels 0..3, ld >= 4; always the two
+ *   CFG halves (without CFG there is nothing to rescale).  workspace: 4-byte aligned, at least
+ *   rcdm_cfg_rescale_workspace_bytes(S, f, H, W) bytes (0 for sizes <= 0); factor: device fp32 [S].
+ *   RCDM_EINVAL: null pointers, sizes <= 0, ld < 4, misaligned pointers; RCDM_ESHAPE: S > 65535; RCDM_EWORKSPACE: a short
+ *   workspace — all before any device work.
+ * rcdm_cfg_{ddim,pndm,sigma}_step_scaled: the step entries above with `factor` (device fp32 [S], or NULL: no rescale,
+ *   exactly the unscaled entry — which forwards here with NULL).  A factor of 1.0f is exact: ones == NULL bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rcdm_cfg_rescale_workspace_bytes(int32_t S, int32_t frames, int32_t H, int32_t W);
+int rcdm_cfg_rescale_factor(const void* eps, int32_t ld, int32_t S, int32_t frames, int32_t H, int32_t W,
+                            float guidance_scale, float guidance_rescale, void* workspace, size_t workspace_bytes,
+                            float* factor, void* stream);
+int rcdm_cfg_ddim_step_scaled(const void* eps, int32_t ld, float* latents, int32_t S, int32_t reps,
+                              int32_t frames, int32_t H, int32_t W, float guidance_scale, const float* coef,
+                              const int32_t* step_counter, const float* factor, void* stream);
+int rcdm_cfg_pndm_step_scaled(const void* eps, int32_t ld, float* latents, float* history, int32_t S, int32_t reps,
+                              int32_t frames, int32_t H, int32_t W, float guidance_scale, const float* table,
+                              const int32_t* step_counter, const float* factor, void* stream);
+int rcdm_cfg_sigma_step_scaled(const void* eps, int32_t ld, float* latents, float* model_in, float* history,
+                               const float* noise, int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W,
+                               float guidance_scale, const float* table, const int32_t* step_counter,
+                               const float* factor, void* stream);
 /* Stage-1 prior, per step of prior_pipeline.py:311-344.
  * rcdm_prior_assemble: tok[(b, l)] (f16, B*L rows of C) <- base rows, except l == time_row <- temb (one fp32 row of C);
  *   x16[b] (f16, E) <- latents[b % n_lat] (fp32): the `torch.cat([latents] * 2)` of :314 and the sequence concat of

@@ -117,9 +117,12 @@ __global__ void rows_to_ncfhw_kernel(const f16* __restrict__ rows, int ld, int b
   out[idx] = (float)rows[((size_t)s * fhw + rem) * ld + c];
 }
 
-// thread per latent element (s, c, f, y, x)
+// thread per latent element (s, c, f, y, x).  SCALED (all three step kernels): the combined prediction of story s is multiplied
+// by factor[s] (guidance rescale, guide.hip) before anything else reads it; the unscaled instantiation is the kernel as it was.
+template <bool SCALED>
 __global__ void cfg_ddim_kernel(const f16* __restrict__ eps, int ld, float* lat, int S, int reps, int F, int H, int W,
-                                float gs, const float* __restrict__ coef, const int* __restrict__ step) {
+                                float gs, const float* __restrict__ coef, const int* __restrict__ step,
+                                const float* __restrict__ factor) {
   const size_t hw = (size_t)H * W, fhw = hw * F;
   const size_t total = (size_t)S * 4 * fhw;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -132,6 +135,7 @@ __global__ void cfg_ddim_kernel(const f16* __restrict__ eps, int ld, float* lat,
     const float ec = (float)eps[((size_t)(S + s) * fhw + rem) * ld + c];
     e = e + gs * (ec - e);
   }
+  if (SCALED) e *= factor[s];
   const float* k = coef + (size_t)(*step) * 4;
   const float x = lat[idx];
   const float x0 = (x - k[1] * e) / k[0];
@@ -143,8 +147,10 @@ __global__ void cfg_ddim_kernel(const f16* __restrict__ eps, int ld, float* lat,
 // (a, b, w_now, w1, w2, w3, slot_now, s1, s2, s3, mode, -):  e' = w_now e + w1 hist[s1] + w2 hist[s2] + w3 hist[s3];
 // x' = a x_src + b e' with x_src = the saved first sample in mode 2 (the repeated second call), x otherwise; mode 1 saves x;
 // slot_now >= 0 stores e.  hist: fp32 [5][total] — four prediction slots + the saved sample.
+template <bool SCALED>
 __global__ void cfg_pndm_kernel(const f16* __restrict__ eps, int ld, float* lat, float* __restrict__ hist, int S, int reps, int F,
-                                int H, int W, float gs, const float* __restrict__ tab, const int* __restrict__ step) {
+                                int H, int W, float gs, const float* __restrict__ tab, const int* __restrict__ step,
+                                const float* __restrict__ factor) {
   const size_t hw = (size_t)H * W, fhw = hw * F;
   const size_t total = (size_t)S * 4 * fhw;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,6 +163,7 @@ __global__ void cfg_pndm_kernel(const f16* __restrict__ eps, int ld, float* lat,
     const float ec = (float)eps[((size_t)(S + s) * fhw + rem) * ld + c];
     e = e + gs * (ec - e);
   }
+  if (SCALED) e *= factor[s];
   const float* k = tab + (size_t)(*step) * 12;
   const int slot = (int)k[6], mode = (int)k[10];
   float mo = k[2] * e;
@@ -176,12 +183,12 @@ __global__ void cfg_pndm_kernel(const f16* __restrict__ eps, int ld, float* lat,
 // when VEC), the CFG combine is done once, then the 4 channel planes of latents / history / noise / model_in are walked
 // (consecutive threads -> consecutive addresses in every plane).  A history slot is read only under a non-zero weight
 // and a noise row only under a non-zero c, so neither needs initialisation; slot indices outside 0..2 are ignored.
-template <bool VEC>
+template <bool VEC, bool SCALED>
 __global__ __launch_bounds__(256) void cfg_sigma_kernel(const f16* __restrict__ eps, int ld, float* __restrict__ lat,
                                                         float* __restrict__ model_in, float* __restrict__ hist,
                                                         const float* __restrict__ noise, int S, int reps, size_t fhw,
                                                         float gs, const float* __restrict__ tab,
-                                                        const int* __restrict__ step) {
+                                                        const int* __restrict__ step, const float* __restrict__ factor) {
   const size_t total = (size_t)S * 4 * fhw;
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= (size_t)S * fhw) return;
@@ -210,6 +217,11 @@ __global__ __launch_bounds__(256) void cfg_sigma_kernel(const f16* __restrict__ 
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) e[c] = e[c] + gs * (v[c] - e[c]);
+  }
+  if (SCALED) {
+    const float fs = factor[s];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) e[c] *= fs;
   }
   const int st = *step;
   const float* k = tab + (size_t)st * 16;
@@ -495,43 +507,69 @@ int rcdm_rows_to_ncfhw(const void* rows, int32_t ld, int32_t b, int32_t C, int32
   return rcdm_check_launch();
 }
 
-int rcdm_cfg_ddim_step(const void* eps, int32_t ld, float* latents, int32_t S, int32_t reps, int32_t frames, int32_t H,
-                       int32_t W, float guidance_scale, const float* coef, const int32_t* step_counter, void* stream) {
+int rcdm_cfg_ddim_step_scaled(const void* eps, int32_t ld, float* latents, int32_t S, int32_t reps, int32_t frames, int32_t H,
+                              int32_t W, float guidance_scale, const float* coef, const int32_t* step_counter,
+                              const float* factor, void* stream) {
   if (!eps || !latents || !coef || !step_counter) return RCDM_EINVAL;
   if (S <= 0 || (reps != 1 && reps != 2) || frames <= 0 || H <= 0 || W <= 0 || ld < 4) return RCDM_EINVAL;
   const size_t total = (size_t)S * 4 * frames * H * W;
-  hipLaunchKernelGGL(cfg_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const f16*)eps, ld, latents, S, reps, frames, H, W, guidance_scale, coef, step_counter);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (factor)
+    hipLaunchKernelGGL(cfg_ddim_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)eps, ld, latents, S, reps,
+                       frames, H, W, guidance_scale, coef, step_counter, factor);
+  else
+    hipLaunchKernelGGL(cfg_ddim_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)eps, ld, latents, S, reps,
+                       frames, H, W, guidance_scale, coef, step_counter, factor);
+  return rcdm_check_launch();
+}
+
+int rcdm_cfg_ddim_step(const void* eps, int32_t ld, float* latents, int32_t S, int32_t reps, int32_t frames, int32_t H,
+                       int32_t W, float guidance_scale, const float* coef, const int32_t* step_counter, void* stream) {
+  return rcdm_cfg_ddim_step_scaled(eps, ld, latents, S, reps, frames, H, W, guidance_scale, coef, step_counter, nullptr, stream);
+}
+
+int rcdm_cfg_pndm_step_scaled(const void* eps, int32_t ld, float* latents, float* history, int32_t S, int32_t reps,
+                              int32_t frames, int32_t H, int32_t W, float guidance_scale, const float* table,
+                              const int32_t* step_counter, const float* factor, void* stream) {
+  if (!eps || !latents || !history || !table || !step_counter) return RCDM_EINVAL;
+  if (S <= 0 || (reps != 1 && reps != 2) || frames <= 0 || H <= 0 || W <= 0 || ld < 4) return RCDM_EINVAL;
+  const size_t total = (size_t)S * 4 * frames * H * W;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (factor)
+    hipLaunchKernelGGL(cfg_pndm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)eps, ld, latents, history, S,
+                       reps, frames, H, W, guidance_scale, table, step_counter, factor);
+  else
+    hipLaunchKernelGGL(cfg_pndm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)eps, ld, latents, history, S,
+                       reps, frames, H, W, guidance_scale, table, step_counter, factor);
   return rcdm_check_launch();
 }
 
 int rcdm_cfg_pndm_step(const void* eps, int32_t ld, float* latents, float* history, int32_t S, int32_t reps, int32_t frames,
                        int32_t H, int32_t W, float guidance_scale, const float* table, const int32_t* step_counter, void* stream) {
-  if (!eps || !latents || !history || !table || !step_counter) return RCDM_EINVAL;
+  return rcdm_cfg_pndm_step_scaled(eps, ld, latents, history, S, reps, frames, H, W, guidance_scale, table, step_counter,
+                                   nullptr, stream);
+}
+
+int rcdm_cfg_sigma_step_scaled(const void* eps, int32_t ld, float* latents, float* model_in, float* history, const float* noise,
+                               int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W, float guidance_scale,
+                               const float* table, const int32_t* step_counter, const float* factor, void* stream) {
+  if (!eps || !latents || !model_in || !history || !table || !step_counter) return RCDM_EINVAL;
   if (S <= 0 || (reps != 1 && reps != 2) || frames <= 0 || H <= 0 || W <= 0 || ld < 4) return RCDM_EINVAL;
-  const size_t total = (size_t)S * 4 * frames * H * W;
-  hipLaunchKernelGGL(cfg_pndm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const f16*)eps, ld, latents, history, S, reps, frames, H, W, guidance_scale, table, step_counter);
+  const size_t fhw = (size_t)frames * H * W;
+  const size_t n = (size_t)S * fhw;
+  const bool vec = (ld & 3) == 0 && ((uintptr_t)eps & 7) == 0;
+  auto kernel = vec ? (factor ? cfg_sigma_kernel<true, true> : cfg_sigma_kernel<true, false>)
+                    : (factor ? cfg_sigma_kernel<false, true> : cfg_sigma_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const f16*)eps, ld, latents,
+                     model_in, history, noise, S, reps, fhw, guidance_scale, table, step_counter, factor);
   return rcdm_check_launch();
 }
 
 int rcdm_cfg_sigma_step(const void* eps, int32_t ld, float* latents, float* model_in, float* history, const float* noise,
                         int32_t S, int32_t reps, int32_t frames, int32_t H, int32_t W, float guidance_scale,
                         const float* table, const int32_t* step_counter, void* stream) {
-  if (!eps || !latents || !model_in || !history || !table || !step_counter) return RCDM_EINVAL;
-  if (S <= 0 || (reps != 1 && reps != 2) || frames <= 0 || H <= 0 || W <= 0 || ld < 4) return RCDM_EINVAL;
-  const size_t fhw = (size_t)frames * H * W;
-  const size_t n = (size_t)S * fhw;
-  const bool vec = (ld & 3) == 0 && ((uintptr_t)eps & 7) == 0;
-  if (vec)
-    hipLaunchKernelGGL(cfg_sigma_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps, ld, latents, model_in, history, noise, S, reps, fhw, guidance_scale, table,
-                       step_counter);
-  else
-    hipLaunchKernelGGL(cfg_sigma_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps, ld, latents, model_in, history, noise, S, reps, fhw, guidance_scale, table,
-                       step_counter);
-  return rcdm_check_launch();
+  return rcdm_cfg_sigma_step_scaled(eps, ld, latents, model_in, history, noise, S, reps, frames, H, W, guidance_scale, table,
+                                    step_counter, nullptr, stream);
 }
 
 int rcdm_prior_assemble(const void* base, const float* temb, const float* latents, int32_t n_lat, void* tok, void* x16,

@@ -178,6 +178,11 @@ SYMBOLS = {
     "rcdm_cfg_ddim_step": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "rcdm_cfg_pndm_step": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "rcdm_cfg_sigma_step": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "rcdm_cfg_rescale_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "rcdm_cfg_rescale_factor": (C.c_int, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _SZ, _P, _P]),
+    "rcdm_cfg_ddim_step_scaled": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "rcdm_cfg_pndm_step_scaled": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "rcdm_cfg_sigma_step_scaled": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "rcdm_prior_assemble": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rcdm_cfg_unclip_step": (C.c_int, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
     "rcdm_embed_tokens": (C.c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
@@ -580,6 +585,32 @@ def cfg_pndm_step(eps, ld, lat, hist, S, reps, frames, H, W, gs, table, step, st
 def cfg_sigma_step(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step, stream=None):
     _check(load().rcdm_cfg_sigma_step(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step,
                                       stream_ptr() if stream is None else stream), "rcdm_cfg_sigma_step")
+
+
+def cfg_rescale_workspace_bytes(S, frames, H, W):
+    return load().rcdm_cfg_rescale_workspace_bytes(S, frames, H, W)
+
+
+def cfg_rescale_factor(eps, ld, S, frames, H, W, gs, phi, ws, ws_bytes, factor, stream=None):
+    """factor[s] = phi * std(eps_c) / std(eps_u + gs (eps_c - eps_u)) + 1 - phi per story (guidance rescale), two launches."""
+    _check(load().rcdm_cfg_rescale_factor(eps, ld, S, frames, H, W, gs, phi, ws, ws_bytes, factor,
+                                          stream_ptr() if stream is None else stream), "rcdm_cfg_rescale_factor")
+
+
+def cfg_pndm_step_scaled(eps, ld, lat, hist, S, reps, frames, H, W, gs, table, step, factor, stream=None):
+    _check(load().rcdm_cfg_pndm_step_scaled(eps, ld, lat, hist, S, reps, frames, H, W, gs, table, step, factor or None,
+                                            stream_ptr() if stream is None else stream), "rcdm_cfg_pndm_step_scaled")
+
+
+def cfg_sigma_step_scaled(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step, factor, stream=None):
+    _check(load().rcdm_cfg_sigma_step_scaled(eps, ld, lat, model_in, hist, noise, S, reps, frames, H, W, gs, table, step,
+                                             factor or None, stream_ptr() if stream is None else stream),
+           "rcdm_cfg_sigma_step_scaled")
+
+
+def cfg_ddim_step_scaled(eps, ld, lat, S, reps, frames, H, W, gs, coef, step, factor, stream=None):
+    _check(load().rcdm_cfg_ddim_step_scaled(eps, ld, lat, S, reps, frames, H, W, gs, coef, step, factor or None,
+                                            stream_ptr() if stream is None else stream), "rcdm_cfg_ddim_step_scaled")
 
 
 def cfg_ddim_step(eps, ld, lat, S, reps, frames, H, W, gs, coef, step, stream=None):

@@ -15,14 +15,21 @@ from .engine import CIN_PAD, full_rank_runs
 
 class DenoiseLoop:
     def __init__(self, unet, stories, frames, height, width, ctx_len, guidance_scale, scheduler, num_steps,
-                 share_cfg_prefix=True, cfg_split=None, rank1_context=True):
-        """cfg_split (rcdms_amd.dist.CfgSplit or anything with .half and .allgather(send_ptr, recv_ptr, nbytes)): the
+                 share_cfg_prefix=True, cfg_split=None, rank1_context=True, guidance_rescale=0.0, eta=0.0):
+        """guidance_rescale (phi): with classifier-free guidance on, the guided prediction of every story is rescaled towards
+        the standard deviation of its conditional one (rcdms_amd.scheduler.rescale_noise_cfg) — two more launches ahead of
+        the step (rcdm_cfg_rescale_factor), which then takes the per-story factors; ignored without CFG, as diffusers does.
+        eta: stochastic DDIM for a DDIMScheduler (its eta_table() through the table step, one N(0, I) draw per step staged
+        by load()); every other scheduler type ignores it, as the reference's prepare_extra_step_kwargs does.
+        cfg_split (rcdms_amd.dist.CfgSplit or anything with .half and .allgather(send_ptr, recv_ptr, nbytes)): the
         two-GPUs-per-story latency mode — this rank evaluates only CFG half `half` of the UNet (batch S instead of 2S),
         the halves' noise predictions are all-gathered inside the step graph and every rank applies the same CFG +
         DDIM update.  load() still takes the full CFG batch of mask / masked latents / context."""
         self.unet, self.S, self.f, self.H, self.W = unet, stories, frames, height, width
         self.gs = float(guidance_scale)
         self.reps = 2 if guidance_scale > 1.0 else 1
+        self.phi = float(guidance_rescale) if self.reps == 2 else 0.0
+        self.eta = 0.0
         self.T = int(num_steps)
         dev = unet.device
         self.device = dev
@@ -83,10 +90,29 @@ class DenoiseLoop:
                 a_t, a_p = ac[t], (ac[prev] if prev >= 0 else final)
                 rows.append([a_t.sqrt(), (1 - a_t).sqrt(), a_p.sqrt(), (1 - a_p).sqrt()])
             self.coef = torch.tensor(rows, dtype=torch.float32).to(dev)
+            if float(eta) != 0.0:
+                # stochastic DDIM is linear in x, e and one noise tensor: a row of the table kernel, no step kernel of its own
+                if not hasattr(scheduler, "eta_table"):
+                    raise NotImplementedError(f"{type(scheduler).__name__}: eta > 0 needs rcdms_amd.scheduler.DDIMScheduler "
+                                              "(its eta_table())")
+                self.eta = float(eta)
+                self.sigma = True
+                self.coef = scheduler.eta_table(self.eta).to(dev)
+                self.hist = torch.empty(3, stories * 4 * frames * height * width, dtype=torch.float32, device=dev)
+                self.multistep = False
+                self._cin0 = 1.0
+                self.model_in = torch.zeros(stories, 4, frames, height, width, dtype=torch.float32, device=dev)
+                self.noise = torch.zeros(self.T, stories, 4, frames, height, width, dtype=torch.float32, device=dev)
         self.ts_dev = ts.to(torch.float32).to(dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.init_noise_sigma = float(getattr(scheduler, "init_noise_sigma", 1.0))
 
+        self.factor = self._guide_ws = None
+        if self.phi != 0.0:
+            # per-story rescale factors and the fixed-order partial sums they are made from (written anew every step)
+            self.factor = torch.empty(stories, dtype=torch.float32, device=dev)
+            self._guide_ws = torch.empty(hip.cfg_rescale_workspace_bytes(stories, frames, height, width), dtype=torch.uint8,
+                                         device=dev)
         self.ctx_len = ctx_len
         S, R, f, H, W = stories, self.reps, frames, height, width
         self.lat = torch.zeros(S, 4, f, H, W, dtype=torch.float32, device=dev)
@@ -152,7 +178,22 @@ class DenoiseLoop:
     def _sched_step(self, eps_ptr, ld):
         """CFG combine + scheduler.step (RCDMs_pipeline.py:492-497) on the device-resident latents, row `step` of the table."""
         S, R, f, H, W = self.S, self.reps, self.f, self.H, self.W
-        if self.sigma:
+        if self.factor is not None:
+            # guidance rescale: the factors first, from the same eps rows (the gathered ones in CFG-split mode)
+            hip.cfg_rescale_factor(eps_ptr, ld, S, f, H, W, self.gs, self.phi, self._guide_ws.data_ptr(),
+                                   self._guide_ws.numel(), self.factor.data_ptr())
+            k = self.factor.data_ptr()
+            if self.sigma:
+                hip.cfg_sigma_step_scaled(eps_ptr, ld, self.lat.data_ptr(), self.model_in.data_ptr(), self.hist.data_ptr(),
+                                          0 if self.noise is None else self.noise.data_ptr(), S, R, f, H, W, self.gs,
+                                          self.coef.data_ptr(), self.step_dev.data_ptr(), k)
+            elif self.pndm:
+                hip.cfg_pndm_step_scaled(eps_ptr, ld, self.lat.data_ptr(), self.hist.data_ptr(), S, R, f, H, W, self.gs,
+                                         self.coef.data_ptr(), self.step_dev.data_ptr(), k)
+            else:
+                hip.cfg_ddim_step_scaled(eps_ptr, ld, self.lat.data_ptr(), S, R, f, H, W, self.gs, self.coef.data_ptr(),
+                                         self.step_dev.data_ptr(), k)
+        elif self.sigma:
             hip.cfg_sigma_step(eps_ptr, ld, self.lat.data_ptr(), self.model_in.data_ptr(), self.hist.data_ptr(),
                                0 if self.noise is None else self.noise.data_ptr(), S, R, f, H, W, self.gs,
                                self.coef.data_ptr(), self.step_dev.data_ptr())
@@ -190,7 +231,7 @@ class DenoiseLoop:
     def load(self, latents, mask, masked_latents, ctx, *, noise=None, generator=None):
         """Stage the loop inputs in HBM (this is outside the timed hot loop: inputs resident when it starts).  latents: the
         unit-variance initial noise (scaled by the scheduler's init_noise_sigma here).  noise / generator: Euler-ancestral
-        only — the T per-step noise tensors (T, S, 4, f, H, W), else drawn as T randn calls of shape (S, 4, f, H, W) in step
+        and DDIM with eta > 0 only — the T per-step noise tensors (T, S, 4, f, H, W), else drawn as T randn calls of shape (S, 4, f, H, W) in step
         order from `generator`, on its device (what the scheduler's step() draws, one call per step)."""
         S, R = self.S, self.reps
         assert tuple(latents.shape) == tuple(self.lat.shape), (latents.shape, self.lat.shape)

@@ -86,12 +86,43 @@ class DDIMScheduler:
             rows.append([a_t.sqrt(), (1 - a_t).sqrt(), a_p.sqrt(), (1 - a_p).sqrt()])
         return torch.tensor(rows, dtype=torch.float32)
 
-    def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
-             variance_noise=None, return_dict=True):
+    def _alphas(self, t):
+        """(a_t, a_prev) of inference timestep t, fp64 tensors."""
+        prev = int(t) - self.config.num_train_timesteps // self.num_inference_steps
+        ac = self.alphas_cumprod.double()
+        return ac[int(t)], (ac[prev] if prev >= 0 else self.final_alpha_cumprod.double())
+
+    def eta_table(self, eta):
+        """Stochastic DDIM (eta > 0; DDIM paper eq. (12) / (16), diffusers 0.24.0 `step`) as rows of rcdm_cfg_sigma_step:
+        fp32 [n][16] in the SIGMA_ROW layout (module comment further down), computed in fp64.  With
+          var = (1 - a_p) / (1 - a_t) (1 - a_t / a_p),  sigma = eta sqrt(var),
+          x' = sqrt(a_p) x0 + sqrt(1 - a_p - sigma^2) e + sigma z,   x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t)
+        the update is linear in x, e and z:  d = e (px 0, pe 1),  a = sqrt(a_p / a_t),
+        b = sqrt(1 - a_p - sigma^2) - sqrt(a_p) sqrt(1 - a_t) / sqrt(a_t),  c = sigma,  cin = cin_next = 1, no history slot.
+        clip_sample is not part of the table (DenoiseLoop refuses it)."""
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if eta != 0.0:
-            raise NotImplementedError("eta > 0 (stochastic DDIM) is not used by the reference")
+        eta = float(eta)
+        rows = []
+        for t in self.timesteps.tolist():
+            a_t, a_p = (float(v) for v in self._alphas(t))
+            var = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+            sig = eta * max(var, 0.0) ** 0.5
+            row = [0.0] * 16
+            row[0:9] = [0.0, 1.0, (a_p / a_t) ** 0.5,
+                        max(1 - a_p - sig * sig, 0.0) ** 0.5 - a_p ** 0.5 * (1 - a_t) ** 0.5 / a_t ** 0.5,
+                        0.0, 0.0, 0.0, sig, 1.0]
+            row[9:14] = [-1.0, -1.0, -1.0, -1.0, 1.0]
+            rows.append(row)
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+    def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
+             variance_noise=None, return_dict=True):
+        """eta > 0: sigma_t = eta sqrt(var_t) of noise is added, `variance_noise` if given, else one randn of model_output's
+        shape from `generator` (on the generator's device, as diffusers' randn_tensor) — drawn at every step, the last one
+        included, where sigma_t = 0 under set_alpha_to_one."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         c = self.config
         t = int(timestep)
         prev = t - c.num_train_timesteps // self.num_inference_steps
@@ -102,10 +133,42 @@ class DDIMScheduler:
             x0 = x0.clamp(-1.0, 1.0)
         if use_clipped_model_output:   # diffusers 0.24: epsilon is re-derived from the clipped x0 only on request
             model_output = (sample - a_t ** 0.5 * x0) / (1 - a_t) ** 0.5
-        prev_sample = a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * model_output
+        if eta == 0.0:
+            prev_sample = a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * model_output
+        else:
+            if variance_noise is not None and generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or "
+                                 "`variance_noise` stays `None`.")
+            var = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+            sig = eta * var.clamp(min=0) ** 0.5
+            prev_sample = a_p ** 0.5 * x0 + (1 - a_p - sig ** 2).clamp(min=0) ** 0.5 * model_output
+            if variance_noise is None:
+                dev = model_output.device
+                gdev = generator.device if generator is not None else dev
+                variance_noise = torch.randn(model_output.shape, dtype=model_output.dtype, device=gdev,
+                                             generator=generator).to(dev)
+            prev_sample = prev_sample + sig * variance_noise
         if not return_dict:
             return (prev_sample,)
         return DDIMSchedulerOutput(prev_sample=prev_sample, pred_original_sample=x0)
+
+
+def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
+    """Guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", §3.4; diffusers
+    `rescale_noise_cfg`, restated — "parity unpinned"): the guided prediction rescaled to the per-sample standard deviation of
+    the conditional one, mixed back with weight `guidance_rescale`:
+        k = phi std(noise_pred_text) / std(noise_cfg) + (1 - phi),   returns k noise_cfg
+    std over every axis but the first, unbiased (torch.std).  A deliberate guard: where std(noise_cfg) == 0 (a constant
+    prediction) k = 1, where diffusers divides and returns inf / nan.  phi = 0 returns `noise_cfg` itself.  The host-visible
+    form of rcdm_cfg_rescale_factor + rcdm_cfg_*_step_scaled (rcdms_amd/sampler.py)."""
+    if guidance_rescale == 0.0:
+        return noise_cfg
+    dims = list(range(1, noise_cfg.dim()))
+    std_text = noise_pred_text.std(dim=dims, keepdim=True)
+    std_cfg = noise_cfg.std(dim=dims, keepdim=True)
+    zero = std_cfg == 0
+    k = guidance_rescale * (std_text / torch.where(zero, torch.ones_like(std_cfg), std_cfg)) + (1 - guidance_rescale)
+    return noise_cfg * torch.where(zero, torch.ones_like(k), k)
 
 
 @dataclass

@@ -155,10 +155,11 @@ class StoryRunner:
     @torch.no_grad()
     def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
-                 save_dir=None, indices=None, stage2=None, fix_context_order=False):
+                 save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
-        indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1)."""
+        indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
+        guidance_rescale / eta: stage 2's sampling arguments (RCDMsPipeline.__call__); the stage-1 prior has neither."""
         if mode not in ("continue", "visualization"):
             raise ValueError("check mode")                                      # stage1…:180
         if stage2 is None:
@@ -218,5 +219,5 @@ class StoryRunner:
                           proj_embeds_0=[embeds[s, 1:].unsqueeze(1) for s in range(S)], mask_label=label,
                           video_length=FRAMES, height=H, width=W, guidance_scale=guidance_scale, generator=generator,
                           num_inference_steps=num_inference_steps, output_type=output_type,
-                          fix_context_order=fix_context_order).videos
+                          fix_context_order=fix_context_order, guidance_rescale=guidance_rescale, eta=eta).videos
         return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine)

@@ -261,17 +261,17 @@ class RCDMsPipeline:
 
     # ---- the hot loop ----------------------------------------------------------------------------------------------
     def denoise(self, latents, mask, masked_latents, context, num_inference_steps, guidance_scale, callback=None,
-                callback_steps=1, generator=None, noise=None):
+                callback_steps=1, generator=None, noise=None, guidance_rescale=0.0, eta=0.0):
         """latents (S,4,f,h,w) unit-variance noise (DenoiseLoop.load applies init_noise_sigma); mask (R*S,1,f,h,w);
-        masked_latents (R*S,4,f,h,w); context (R*S*f, L, D); generator: the per-step noise of Euler-ancestral."""
+        masked_latents (R*S,4,f,h,w); context (R*S*f, L, D); generator: the per-step noise of Euler-ancestral and of DDIM
+        with eta > 0; guidance_rescale / eta: as DenoiseLoop takes them (both are part of the cached loop's key)."""
         S, _, f, h, w = latents.shape
         key = (S, f, h, w, context.shape[1], float(guidance_scale), int(num_inference_steps), id(self.scheduler),
-               id(self.unet), self.unet._weights_gen)
+               id(self.unet), self.unet._weights_gen, float(guidance_rescale), float(eta))
         if self._loop is None or self._loop_key != key:
             self._loop = DenoiseLoop(self.unet, S, f, h, w, context.shape[1], guidance_scale, self.scheduler,
-                                     num_inference_steps)
-            self._loop_key = (S, f, h, w, context.shape[1], float(guidance_scale), int(num_inference_steps),
-                              id(self.scheduler), id(self.unet), self.unet._weights_gen)
+                                     num_inference_steps, guidance_rescale=guidance_rescale, eta=eta)
+            self._loop_key = key
         self._loop.load(latents, mask, masked_latents, context, noise=noise, generator=generator)
         return self._loop.run(callback=callback, callback_steps=callback_steps)
 
@@ -282,19 +282,20 @@ class RCDMsPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "tensor", return_dict: bool = True,
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: Optional[int] = 1,
-                 fix_context_order: bool = False, png_match: bool = False, **kwargs):
+                 fix_context_order: bool = False, png_match: bool = False, guidance_rescale: float = 0.0, **kwargs):
+        """guidance_rescale (what the reference driver passes, stage2_batchtest_rcdms_model.py:352): Lin et al. 2023 §3.4 on
+        the guided noise prediction, inside the captured step; 0 is off.  eta: stochastic DDIM with a DDIMScheduler (the
+        per-step noise from `generator`), ignored by every other scheduler type (prepare_extra_step_kwargs, :289-298)."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
-        if eta != 0.0:
-            raise NotImplementedError("eta > 0 is not used by the reference and has no fused HIP step")
         if video_length != self.FRAMES:
             raise ValueError(f"a story has exactly {self.FRAMES} frames (reference RCDMs_pipeline.py:261,430,476)")
         if story_count(prompt, video_length) is not None:
             return self._call_stories(prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
                                       num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator,
                                       latents, output_type, return_dict, callback, callback_steps, fix_context_order,
-                                      png_match)
+                                      png_match, guidance_rescale, eta)
         batch_size = 1
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -327,10 +328,11 @@ class RCDMsPipeline:
 
         return self._sample_and_decode(latents, mask5, masked_latents, context, text_embeddings.dtype, num_inference_steps,
                                        guidance_scale, generator, None, callback, callback_steps, output_type, return_dict,
-                                       png_match)
+                                       png_match, guidance_rescale, eta)
 
     def _sample_and_decode(self, latents, mask5, masked_latents, context, dtype, num_inference_steps, guidance_scale,
-                           generator, noise, callback, callback_steps, output_type, return_dict, png_match):
+                           generator, noise, callback, callback_steps, output_type, return_dict, png_match,
+                           guidance_rescale=0.0, eta=0.0):
         """The captured loop on the staged inputs, then the VAE decode by `output_type` (:455-513); the batch axis of
         `latents` is the story axis."""
         with self.progress_bar(total=num_inference_steps) as bar:
@@ -341,7 +343,8 @@ class RCDMsPipeline:
             # prepare_latents applied init_noise_sigma (as the reference does); DenoiseLoop.load applies it itself
             final = self.denoise(latents / self.scheduler.init_noise_sigma, mask5, masked_latents, context,
                                  num_inference_steps, guidance_scale, callback=on_step if (callback is not None) else None,
-                                 callback_steps=1, generator=generator, noise=noise)
+                                 callback_steps=1, generator=generator, noise=noise, guidance_rescale=guidance_rescale,
+                                 eta=eta)
             if callback is None:
                 bar.update(num_inference_steps)
 
@@ -362,7 +365,8 @@ class RCDMsPipeline:
 
     def _call_stories(self, prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
                       num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator, latents,
-                      output_type, return_dict, callback, callback_steps, fix_context_order, png_match):
+                      output_type, return_dict, callback, callback_steps, fix_context_order, png_match,
+                      guidance_rescale=0.0, eta=0.0):
         """`prompt` is S lists of five captions: S stories through one captured loop.  Story s is the single-story call on
         story s's inputs with story s's generator (one generator: the S calls made one after the other with it).  Every
         story's ten context rows and mask rows are built as in that call and then placed at the loop's batch rows r * S + s
@@ -405,6 +409,8 @@ class RCDMsPipeline:
         if per_story:
             mean, std = torch.cat([d.mean for d in dists]), torch.cat([d.std for d in dists])
         need_noise = hasattr(self.scheduler, "sigma_table") and bool(getattr(self.scheduler, "noise_needed", False))
+        # stochastic DDIM draws per step too (the scheduler types that ignore eta have sigma_table() or plms_table())
+        need_noise = need_noise or (float(eta) != 0.0 and hasattr(self.scheduler, "eta_table"))
         T = int(num_inference_steps)
         if need_noise:
             self.scheduler.set_timesteps(T, device=None)
@@ -438,7 +444,7 @@ class RCDMsPipeline:
         noise = torch.cat(noise, dim=1) if need_noise else None         # (T, S, 4, 5, h, w)
         return self._sample_and_decode(torch.cat(lat), mask5, masked_latents, context, dt, num_inference_steps,
                                        guidance_scale, None, noise, callback, callback_steps, output_type, return_dict,
-                                       png_match)
+                                       png_match, guidance_rescale, eta)
 
 
 # stage2_batchtest_rcdms_model.py:30 imports RCDMsPipeline but :246 instantiates AnimationPipeline
