@@ -891,6 +891,49 @@ int rcdm_png_decode(const rcdm_png_file* files, const rcdm_png_idat* idats, int 
                     void* workspace, void* dst, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Frame metrics: n pairs of equally sized uint8 RGB images on the device (HWC; each side with its own pitch, bytes between
+ * rows, and stride, bytes between images — the buffers rcdm_frames_to_u8 and rcdm_image_resample write, the cells of a grid
+ * included) -> per pair and channel the mean SSIM and the sums of squared and absolute differences.  What the stage-2 driver
+ * is set up for and never computes: it imports skimage's structural_similarity (stage2_batchtest_rcdms_model.py:23) and pairs
+ * every generated frame with its resized target (:389-401).  Neither base pointer nor pitch needs any alignment, and no byte
+ * beyond the 3 * W bytes of a row is read.
+ *   ssim  [n][3] float64: scikit-image's structural_similarity(a, b, channel_axis=-1, data_range=255) per channel, K1 = 0.01,
+ *         K2 = 0.03, C1 = (K1 255)^2, C2 = (K2 255)^2.  With F the window mean:
+ *           ux = F(x), uy = F(y), vx = cn (F(x x) - ux ux), vy = cn (F(y y) - uy uy), vxy = cn (F(x y) - ux uy)
+ *           S  = (2 ux uy + C1)(2 vxy + C2) / ((ux ux + uy uy + C1)(vx + vy + C2))
+ *         and the figure is the mean of S over the window positions that lie inside the image (skimage crops the first and
+ *         last (win - 1) / 2 rows and columns; there is no border mode).  Its three-channel mean is skimage's return value.
+ *           RCDM_SSIM_UNIFORM7  skimage's default, a 7 x 7 box.  The five window sums are integers and the variances are
+ *                               NP sum(x x) - sum(x)^2 in integers (NP = 49): nothing cancels in floating point.
+ *           RCDM_SSIM_GAUSS11   gaussian_weights=True, sigma=1.5: win[11] float64 = exp(-i^2 / (2 sigma^2)), i = -5..5,
+ *                               normalised to sum 1 by the caller; separable passes in float64 over the integer products.
+ *                               (win is not read for the box and may be null.)
+ *           sample_covariance   cn = NP / (NP - 1) with NP = 49 / 121 (skimage's use_sample_covariance=True, its default),
+ *                               0: cn = 1.
+ *         Identical images give exactly 1.0.  The sums have a fixed order (no atomics): the same inputs give the same bits.
+ *   sse, sad  [n][3] int64: exact sums over the whole image of (a - b)^2 and |a - b|; the mean squared error (the sum of
+ *         sse's three channels / (3 H W)), PSNR = 10 log10(255^2 / mse) and the mean absolute error are the caller's to derive.
+ *   rcdm_frame_metrics_workspace_bytes  nine 8-byte partials per tile and pair (0 for a descriptor the entry point refuses)
+ *   rcdm_frame_metrics                  two launches on `stream`, no host readback, no allocation.  workspace: 8-byte
+ *                                       aligned, written then read; a and b are only read.
+ * RCDM_EINVAL: null pointers (win with RCDM_SSIM_GAUSS11), n < 1, H or W < 1, an unknown window, a pitch below 3 W, a negative
+ * stride, win / ssim / sse / sad / workspace not 8-byte aligned.  RCDM_ESHAPE: channels != 3, H or W below the window side, a
+ * side above 8192, n > 65535.  RCDM_EWORKSPACE: workspace null or short.  All checked before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_SSIM_UNIFORM7 0
+#define RCDM_SSIM_GAUSS11 1
+typedef struct {
+  int64_t a_pitch, a_stride;       /* bytes between rows / images of a */
+  int64_t b_pitch, b_stride;       /* ... of b */
+  int32_t n, H, W, channels;       /* channels == 3 */
+  int32_t window;                  /* RCDM_SSIM_* */
+  int32_t sample_covariance;       /* non-zero: cn = NP / (NP - 1) */
+} rcdm_metrics_desc;
+size_t rcdm_frame_metrics_workspace_bytes(const rcdm_metrics_desc* d);
+int rcdm_frame_metrics(const rcdm_metrics_desc* d, const void* a, const void* b, const double* win, double* ssim, int64_t* sse,
+                       int64_t* sad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

@@ -110,6 +110,13 @@ class PngIdat(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MetricsDesc(C.Structure):
+    _fields_ = [("a_pitch", C.c_int64), ("a_stride", C.c_int64), ("b_pitch", C.c_int64), ("b_stride", C.c_int64),
+                ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("window", C.c_int32),
+                ("sample_covariance", C.c_int32)]
+
+
+SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
 PNG_RGB, PNG_BGR = 0, 1
 PNG_STATUS = {1: "RCDM_PNG_EZLIB", 2: "RCDM_PNG_ETRUNC", 3: "RCDM_PNG_EBLOCK", 4: "RCDM_PNG_ESTORED", 5: "RCDM_PNG_ECODES",
@@ -198,6 +205,8 @@ SYMBOLS = {
     "rcdm_png_encode_match": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
     "rcdm_png_decode_workspace_bytes": (_SZ, [_P, C.c_int]),
     "rcdm_png_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "rcdm_frame_metrics_workspace_bytes": (_SZ, [C.POINTER(MetricsDesc)]),
+    "rcdm_frame_metrics": (C.c_int, [C.POINTER(MetricsDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -560,6 +569,15 @@ def png_match_workspace_bytes(desc):
 def png_encode_match(desc, src, workspace, dst, sizes, stream=None):
     _check(load().rcdm_png_encode_match(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
            "rcdm_png_encode_match")
+
+
+def frame_metrics_workspace_bytes(desc):
+    return int(load().rcdm_frame_metrics_workspace_bytes(C.byref(desc)))
+
+
+def frame_metrics(desc, a, b, win, ssim, sse, sad, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_frame_metrics(C.byref(desc), a, b, win, ssim, sse, sad, workspace, workspace_bytes,
+                                     stream_ptr() if stream is None else stream), "rcdm_frame_metrics")
 
 
 def assemble_input(lat, mask, masked, S, reps, frames, H, W, out, ld, c_pad, stream=None):

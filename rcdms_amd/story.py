@@ -6,7 +6,8 @@ stage2_batchtest_rcdms_model.py reads them back — one story per pipeline call.
     checks and `place_story_rows`, which puts every story's CFG rows where the captured loops expect them;
   * `write_stage1_embeds`, the files of stage1…:260,264 for a stage-2 process of the old kind;
   * `StoryRunner`: uint8 frames + captions -> CLIP vision forward -> stage 1 -> cosine figure -> hand-off -> stage 2,
-    batched over S, all tensors staying on the device.
+    batched over S, all tensors staying on the device; on request the per-frame SSIM / PSNR / CLIP-I of the generated frames
+    against their targets (rcdms_amd.metrics).
 The hot paths are the two captured loops (rcdms_amd.sampler) at batch S; this module is glue around them."""
 import os
 from dataclasses import dataclass
@@ -95,6 +96,12 @@ class StoryResult:
     image_embeds: torch.Tensor        # (S, 5, E) stage-1 output
     target_embeds: torch.Tensor       # (S, 5, E) CLIP embeddings of the five given frames
     cosine: torch.Tensor              # (S, 5) the figure the stage-1 driver prints (:239,258)
+    ssim: Optional[torch.Tensor] = None    # (S, 5) float64, generated frame against its resized target (metrics=("ssim",))
+    psnr: Optional[torch.Tensor] = None    # (S, 5) float64, inf for identical frames (metrics=("psnr",))
+    clip_i: Optional[torch.Tensor] = None  # (S, 5) cosine of the generated frames' CLIP embeddings and target_embeds ("clip_i")
+
+
+METRICS = ("ssim", "psnr", "clip_i")
 
 
 class StoryRunner:
@@ -155,11 +162,19 @@ class StoryRunner:
     @torch.no_grad()
     def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
-                 save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0):
+                 save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=()):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
-        guidance_rescale / eta: stage 2's sampling arguments (RCDMsPipeline.__call__); the stage-1 prior has neither."""
+        guidance_rescale / eta: stage 2's sampling arguments (RCDMsPipeline.__call__); the stage-1 prior has neither.
+        metrics: any of "ssim", "psnr", "clip_i" — per-frame figures of the generated frames against the five given frames
+        resized to the stage-2 size with Pillow's bilinear filter (the driver's vis_augment, stage2…:390-396), in the result's
+        fields of those names, computed on the device (rcdms_amd.metrics; "clip_i" is one more vision forward).  They need a
+        stage-2 run with output_type="uint8".  metrics=(): nothing more is launched."""
+        metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+        for m in metrics:
+            if m not in METRICS:
+                raise ValueError(f"metric {m!r}: any of {METRICS}")
         if mode not in ("continue", "visualization"):
             raise ValueError("check mode")                                      # stage1…:180
         if stage2 is None:
@@ -169,6 +184,10 @@ class StoryRunner:
                              "there and fails at stage2_batchtest_rcdms_model.py:367 — run mode=\"continue\", or stage2=False")
         if stage2 and self.stage2_pipe is None:
             raise ValueError("stage 2 asked for, but the runner was built without a stage-2 pipeline")
+        if metrics and not stage2:
+            raise ValueError(f"metrics {metrics} compare the frames stage 2 generates with their targets: this call runs no stage 2")
+        if metrics and output_type != "uint8":
+            raise ValueError(f"metrics {metrics} are computed on uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
         frames = torch.as_tensor(frames)
         if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[1] != FRAMES or frames.shape[-1] != 3:
             raise ValueError(f"frames are uint8 (S, {FRAMES}, H, W, 3), got {frames.dtype} {tuple(frames.shape)}")
@@ -220,4 +239,32 @@ class StoryRunner:
                           video_length=FRAMES, height=H, width=W, guidance_scale=guidance_scale, generator=generator,
                           num_inference_steps=num_inference_steps, output_type=output_type,
                           fix_context_order=fix_context_order, guidance_rescale=guidance_rescale, eta=eta).videos
-        return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine)
+        figures = self.story_metrics(videos, frames, target, metrics) if metrics else {}
+        return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures)
+
+    def target_frames(self, frames):
+        """The five given frames of every story at the stage-2 size, uint8 (S, 5, H, W, 3): Pillow's bilinear resize as bytes,
+        one launch for all 5 S frames."""
+        from .image import resampler, to_device_frames
+        S = frames.shape[0]
+        flat, = to_device_frames(frames.reshape(S * FRAMES, *frames.shape[2:]), self.device)
+        ft = self.frame_transform
+        r = resampler(flat.shape[1], flat.shape[2], ft.height, ft.width, ft.resample, None, flat.device)
+        return r.to_uint8(flat, ft.flip_channels).view(S, FRAMES, ft.height, ft.width, 3)
+
+    def story_metrics(self, videos, frames, target_embeds, metrics):
+        """videos: uint8 (S, 5, H, W, 3) as stage 2 returns them; frames: the given uint8 (S, 5, Hs, Ws, 3) on the device.
+        -> {name: (S, 5) tensor} for the names in `metrics`."""
+        from .metrics import frame_metrics
+        S = videos.shape[0]
+        out = {}
+        if "ssim" in metrics or "psnr" in metrics:
+            fm = frame_metrics(videos, self.target_frames(frames))
+            if "ssim" in metrics:
+                out["ssim"] = fm.ssim.view(S, FRAMES)
+            if "psnr" in metrics:
+                out["psnr"] = fm.psnr.view(S, FRAMES)
+        if "clip_i" in metrics:
+            e = self.image_encoder(self._pixels(videos.reshape(S * FRAMES, *videos.shape[2:]))).image_embeds
+            out["clip_i"] = torch.nn.functional.cosine_similarity(e.reshape(S, FRAMES, -1).float(), target_embeds.float(), dim=-1)
+        return out
