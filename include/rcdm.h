@@ -934,6 +934,66 @@ int rcdm_frame_metrics(const rcdm_metrics_desc* d, const void* a, const void* b,
                        int64_t* sad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
+ * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
+ * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the
+ * host for (row lengths, pooled position).  Pinned to the `tokenizers` backend of transformers 5.x on synthetic vocabularies
+ * (tests/golden/tok_*.npz); never run on the real CLIP files.  One launch, one wavefront per caption, no host readback.
+ *   1. added tokens   rows with special != 0 (the bos / eos strings) are matched on the raw bytes, then the other rows (add_tokens;
+ *                     text lower-cased by the caller) on the lower-cased bytes of each stretch between those matches, also
+ *                     inside words.  Leftmost-longest, non-overlapping; each match is the row's id and never merges.
+ *   2. normalise      ASCII letters are lower-cased; whitespace is bytes 9-13 and 32.
+ *   3. split          's|'t|'re|'ve|'m|'ll|'d|[a-z]+|[0-9]|[^whitespace a-z 0-9]+ in order; whitespace dropped.
+ *   4. BPE per word   byte b is byte_ids[b], the word's last byte byte_ids[256 + b] (the </w> form).  Repeat: of the live
+ *                     adjacent pairs that the pair table holds, merge the ONE of lowest rank, leftmost first.
+ *   5. frame          bos_id, the tokens, eos_id, pad_id up to max_length; attention_mask 1 through eos.  truncation != 0 keeps
+ *                     the first max_length - 2 tokens.  With truncation == 0 a longer caption's row is written the same way
+ *                     and lengths[i] > max_length tells the caller, who raises.
+ *   text, offsets   the captions end to end and n + 1 int32 offsets into them (ascending, offsets[n] <= text_bytes)
+ *   byte_ids        int32[512]
+ *   added           n_added rcdm_tok_added rows (may be null when n_added == 0)
+ *   pairs           pair_slots rcdm_tok_pair slots, an open-addressing table with linear probing from
+ *                   rcdm_tok_pair_hash(a, b) & (pair_slots - 1); an empty slot has a == 0xFFFFFFFF; at most half full
+ *   input_ids, attention_mask   int64, row i at element i * ld
+ *   lengths         int32[n]: tokens + 2, not truncated; -1 for a caption the kernel refuses (longer than
+ *                   RCDM_TOK_MAX_CAPTION, a byte >= 0x80, offsets out of order or outside text): its row is that of ""
+ *   pool_index      int32[n][2]: position of the row's largest id (the first of equals: the rule of eos_token_id == 2
+ *                   configurations — a token of add_tokens outranks eos there, as in transformers) and of its first eos_id
+ * rcdm_clip_tokenize_workspace_bytes: a caption's symbols live in LDS, so this is 0 for every descriptor the entry point
+ * takes; it is there so that a later layout can need one.  workspace may be null when it is 0.
+ * RCDM_EINVAL: null pointers, n < 1, max_length < 2, ld < max_length, a negative id, n_added or text_bytes, pair_slots no power
+ * of two, input_ids / attention_mask not 8-byte, pairs not 16-byte, the others not 4-byte aligned.  RCDM_ESHAPE: n >
+ * RCDM_TOK_MAX_CAPTIONS, max_length > RCDM_TOK_MAX_CAPTION + 2, n_added > RCDM_TOK_MAX_ROWS, text_bytes >= 2^31, pair_slots >
+ * 2^26.  RCDM_EWORKSPACE: workspace short (or null when bytes are needed).  All before the device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_TOK_MAX_CAPTION 1024     /* bytes of one caption */
+#define RCDM_TOK_MAX_ADDED 64         /* tokens of add_tokens */
+#define RCDM_TOK_MAX_ROWS 66          /* ... plus the two special strings: rows of the added table */
+#define RCDM_TOK_MAX_ADDED_LEN 32     /* bytes of one row */
+#define RCDM_TOK_MAX_RANK (1 << 22)   /* ranks are below this */
+#define RCDM_TOK_MAX_CAPTIONS (1 << 20)
+typedef struct {
+  uint8_t text[RCDM_TOK_MAX_ADDED_LEN];
+  int32_t len, id, special, reserved;
+} rcdm_tok_added;
+typedef struct {
+  uint32_t a, b, rank, merged;     /* (a, b) -> merged at `rank` */
+} rcdm_tok_pair;
+typedef struct {
+  int64_t ld;                      /* elements between rows of input_ids and attention_mask, >= max_length */
+  int64_t text_bytes;
+  int32_t n, max_length, truncation;
+  int32_t bos_id, eos_id, pad_id;
+  int32_t n_added;
+  uint32_t pair_slots;
+} rcdm_tokenize_desc;
+uint32_t rcdm_tok_pair_hash(uint32_t a, uint32_t b);
+size_t rcdm_clip_tokenize_workspace_bytes(const rcdm_tokenize_desc* d);
+int rcdm_clip_tokenize(const rcdm_tokenize_desc* d, const void* text, const int32_t* offsets, const int32_t* byte_ids,
+                       const rcdm_tok_added* added, const rcdm_tok_pair* pairs, int64_t* input_ids, int64_t* attention_mask,
+                       int32_t* lengths, int32_t* pool_index, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

@@ -34,6 +34,7 @@ from torch import nn
 
 from . import hip
 from .engine import Packer, Plan, Rows, _NS, emit_flash_attn, emit_flash_attn_masked, emit_gemm, emit_layernorm
+from .tokenizer import ClipTokenizer
 
 _ACTS = ("quick_gelu", "gelu")
 TEXT_DEFAULTS = dict(vocab_size=49408, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
@@ -50,6 +51,19 @@ def pooling_index(input_ids, eos_token_id):
     if eos_token_id == 2:
         return ids.argmax(dim=-1)
     return (ids == eos_token_id).int().argmax(dim=-1)
+
+
+def tokenizer_keywords(tokenizer, text_encoder, tok):
+    """What a pipeline's _encode_prompt adds to its text-encoder call: the device-side pooling index and the waiver of the id
+    range check when the ids come from a ClipTokenizer and go to a CLIPTextEncoder, nothing for any other pair (the caller's
+    transformers objects, the tests' stubs).  The waiver is earned here: every id a ClipTokenizer emits is below its len(), so a
+    tokenizer that outgrew the embedding table (add_tokens without resizing it) is a ValueError, not an unchecked gather."""
+    if not (isinstance(tokenizer, ClipTokenizer) and isinstance(text_encoder, CLIPTextEncoder)):
+        return {}
+    if len(tokenizer) > text_encoder.cfg["vocab_size"]:
+        raise ValueError(f"the tokenizer holds {len(tokenizer)} tokens, the text encoder's embedding table "
+                         f"{text_encoder.cfg['vocab_size']} rows: resize the table after add_tokens")
+    return dict(pool_index=tok.pool_index, ids_checked=True)
 
 
 class ClipOutput(dict):
@@ -212,13 +226,16 @@ class CLIPTextEncoder(_Encoder16):
     def max_position_embeddings(self):
         return self.text_model.embeddings.position_embedding.weight.shape[0]
 
-    def check_ids(self, input_ids):
-        """The host-side guard of rcdm_embed_tokens (the kernel clamps nothing): ValueError before any launch."""
+    def check_shape(self, input_ids):
         if input_ids.dim() != 2 or input_ids.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"input_ids must be an integer (B, L) tensor, got {tuple(input_ids.shape)} {input_ids.dtype}")
         B, L = input_ids.shape
         if B < 1 or L < 1 or L > self.max_position_embeddings:
             raise ValueError(f"sequence length {L} outside the position table ({self.max_position_embeddings} rows)")
+
+    def check_ids(self, input_ids):
+        """The host-side guard of rcdm_embed_tokens (the kernel clamps nothing): ValueError before any launch."""
+        self.check_shape(input_ids)
         ids = input_ids.detach().cpu()
         lo, hi = int(ids.min()), int(ids.max())
         if lo < 0 or hi >= self.cfg["vocab_size"]:
@@ -227,17 +244,34 @@ class CLIPTextEncoder(_Encoder16):
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, output_attentions=None,
-                output_hidden_states=None, return_dict=True, **_):
-        ids = self.check_ids(input_ids)
+                output_hidden_states=None, return_dict=True, pool_index=None, ids_checked=False, **_):
+        """pool_index: device int (B, 2) — per row the position of the largest id and of the first eos, what ClipTokenizer
+        returns — in place of the host-computed pooling index.  ids_checked=True: the caller vouches that every id lies inside
+        the vocabulary (a ClipTokenizer whose len() fits the embedding table), so the range check's device -> host copy is
+        skipped.  With both, a forward waits for nothing.  With neither, exactly the path as it was."""
+        if ids_checked:
+            self.check_shape(input_ids)
+            ids = None
+        else:
+            ids = self.check_ids(input_ids)
+        if pool_index is not None and (pool_index.device != input_ids.device or tuple(pool_index.shape) != (input_ids.shape[0], 2)
+                                       or pool_index.dtype not in (torch.int32, torch.int64)):
+            raise ValueError(f"pool_index must be an integer (B, 2) tensor on the ids' device, got {tuple(pool_index.shape)} "
+                             f"{pool_index.dtype} on {pool_index.device}")
         if self.device.type != "cuda" or input_ids.device.type != "cuda":
             raise hip.RcdmError(f"CLIPTextEncoder runs on the HIP path only (module on {self.device}, ids on {input_ids.device})")
         if attention_mask is not None or position_ids is not None:
             raise NotImplementedError("the pipelines pass input_ids only (causal mask, positions 0 .. L-1)")
         w = self._weights(pack_text)
-        prog = self._programs.get(tuple(ids.shape))
+        shape = tuple(input_ids.shape)
+        prog = self._programs.get(shape)
         if prog is None:
-            prog = self._programs[tuple(ids.shape)] = ClipTextProgram(self.cfg, w, ids.shape[0], ids.shape[1], self.device)
-        last, pooled, emb = prog.forward(input_ids, pooling_index(ids, self.cfg["eos_token_id"]))
+            prog = self._programs[shape] = ClipTextProgram(self.cfg, w, shape[0], shape[1], self.device)
+        if pool_index is not None:
+            pool = pool_index[:, 0 if self.cfg["eos_token_id"] == 2 else 1]
+        else:
+            pool = pooling_index(input_ids if ids is None else ids, self.cfg["eos_token_id"])
+        last, pooled, emb = prog.forward(input_ids, pool)
         out = ClipOutput(last_hidden_state=last, pooler_output=pooled, text_embeds=emb, hidden_states=None, attentions=None)
         return out if return_dict else (emb, last) if emb is not None else (last, pooled)
 
@@ -405,13 +439,17 @@ class ClipTextProgram:
             self._ws = torch.zeros(max(hip.gemm_workspace_bytes(self._d_proj), 256), dtype=torch.uint8, device=self.device)
 
     def forward(self, input_ids, pool_idx):
-        """input_ids: device (B, L) integers, already range-checked; pool_idx: host (B,) positions.  -> fp32 device tensors
+        """input_ids: device (B, L) integers, already range-checked; pool_idx: (B,) positions, on the host or (ClipTokenizer's)
+        on the device.  -> fp32 device tensors
         (last_hidden_state (B, L, C), pooled (B, C), text_embeds (B, P) | None)."""
         B, L, C = self.B, self.L, self.C
         self.ids.copy_(input_ids.reshape(-1))
         self.plan.run()
         last16 = _rows_view(self.out, B * L, C)
-        flat = (torch.arange(B) * L + pool_idx).to(self.device)
+        if pool_idx.is_cuda:
+            flat = torch.arange(B, device=self.device) * L + pool_idx.long()
+        else:
+            flat = (torch.arange(B) * L + pool_idx).to(self.device)
         torch.index_select(last16, 0, flat, out=self.pool16)       # plumbing (M = B): the pooled rows, gathered by position
         emb = None
         if self.P:

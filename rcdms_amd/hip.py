@@ -116,6 +116,17 @@ class MetricsDesc(C.Structure):
                 ("sample_covariance", C.c_int32)]
 
 
+class TokAdded(C.Structure):
+    _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TokenizeDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("text_bytes", C.c_int64), ("n", C.c_int32), ("max_length", C.c_int32), ("truncation", C.c_int32),
+                ("bos_id", C.c_int32), ("eos_id", C.c_int32), ("pad_id", C.c_int32), ("n_added", C.c_int32),
+                ("pair_slots", C.c_uint32)]
+
+
+TOK_MAX_CAPTION, TOK_MAX_ADDED, TOK_MAX_ROWS, TOK_MAX_ADDED_LEN, TOK_MAX_RANK, TOK_MAX_CAPTIONS = 1024, 64, 66, 32, 1 << 22, 1 << 20
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
 PNG_RGB, PNG_BGR = 0, 1
@@ -207,6 +218,9 @@ SYMBOLS = {
     "rcdm_png_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rcdm_frame_metrics_workspace_bytes": (_SZ, [C.POINTER(MetricsDesc)]),
     "rcdm_frame_metrics": (C.c_int, [C.POINTER(MetricsDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
+    "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_xattn_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rcdm_xattn_pack_kv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rcdm_xattn": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P]),
@@ -569,6 +583,17 @@ def png_match_workspace_bytes(desc):
 def png_encode_match(desc, src, workspace, dst, sizes, stream=None):
     _check(load().rcdm_png_encode_match(C.byref(desc), src, workspace, dst, sizes, stream_ptr() if stream is None else stream),
            "rcdm_png_encode_match")
+
+
+def clip_tokenize_workspace_bytes(desc):
+    return int(load().rcdm_clip_tokenize_workspace_bytes(C.byref(desc)))
+
+
+def clip_tokenize(desc, text, offsets, byte_ids, added, pairs, input_ids, attention_mask, lengths, pool_index, workspace=0,
+                  workspace_bytes=0, stream=None):
+    _check(load().rcdm_clip_tokenize(C.byref(desc), text, offsets, byte_ids, added, pairs, input_ids, attention_mask, lengths,
+                                     pool_index, workspace, workspace_bytes, stream_ptr() if stream is None else stream),
+           "rcdm_clip_tokenize")
 
 
 def frame_metrics_workspace_bytes(desc):

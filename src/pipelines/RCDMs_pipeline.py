@@ -19,6 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from rcdms_amd.clip import tokenizer_keywords
 from rcdms_amd.sampler import DenoiseLoop
 from rcdms_amd.story import check_story_axis, place_story_rows, story_count, story_generators
 from ..models.unet import UNet3DConditionModel, _Config
@@ -122,9 +123,9 @@ class RCDMsPipeline:
         max_len = self.text_encoder.max_position_embeddings
 
         def embed(texts):
-            ids = self.tokenizer(texts, padding="max_length", max_length=max_len, truncation=False,
-                                 return_tensors="pt").input_ids
-            return self.text_encoder(ids.to(device)).last_hidden_state
+            tok = self.tokenizer(texts, padding="max_length", max_length=max_len, truncation=False, return_tensors="pt")
+            return self.text_encoder(tok.input_ids.to(device),
+                                     **tokenizer_keywords(self.tokenizer, self.text_encoder, tok)).last_hidden_state
 
         text = embed(prompt)
         if not do_classifier_free_guidance:

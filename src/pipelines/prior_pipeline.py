@@ -10,6 +10,7 @@ from typing import Callable, Dict, List, Optional, Union
 
 import torch
 
+from rcdms_amd.clip import tokenizer_keywords
 from rcdms_amd.sampler import PriorLoop
 from rcdms_amd.story import check_story_axis, story_count, story_generators
 from src.models.myprior_transformer import MyPriorTransformer
@@ -79,7 +80,7 @@ class Seq_Inpaint_Prior_Pipeline:
 
         def encode(texts):
             tok = self.tokenizer(texts, padding="max_length", max_length=max_len, truncation=True, return_tensors="pt")
-            out = self.text_encoder(tok.input_ids.to(device))
+            out = self.text_encoder(tok.input_ids.to(device), **tokenizer_keywords(self.tokenizer, self.text_encoder, tok))
             return out.text_embeds, out.last_hidden_state, tok.attention_mask.bool().to(device)
 
         emb, hid, mask = encode(prompt)
