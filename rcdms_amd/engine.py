@@ -26,5 +26,5 @@ from .packer import (MSUB_SCORE_LIMIT, Packer, attn_score_bound, pack_attention,
                      pack_resnet, pack_transformer)
 from .emit_blocks import (CHAIN_MIN_ROWS, emit_basic_block, emit_ctx_kv, emit_ff, emit_motion, emit_rank1_ctx,   # noqa: F401
                           emit_resnet, emit_rowchain, emit_transformer, ffz_rows, full_rank_runs)
-from .unet_program import CIN_PAD, COUT_PAD, UNetProgram                                             # noqa: F401
+from .unet_program import CIN_PAD, COUT_PAD, UNetProgram, plan_rank1_runs                            # noqa: F401
 from .eager import ncfhw_from_rows, rows_from_ncfhw, run_block, run_tokens                           # noqa: F401

@@ -10,7 +10,7 @@ import torch
 
 from . import hip
 from . import switches as SW
-from .engine import CIN_PAD, full_rank_runs
+from .engine import CIN_PAD, full_rank_runs, plan_rank1_runs
 
 
 class DenoiseLoop:
@@ -127,13 +127,34 @@ class DenoiseLoop:
             raise ValueError("cfg_split needs classifier-free guidance (guidance_scale > 1)")
         self.share_allowed = share_cfg_prefix and cfg_split is None
         self.rank1_allowed = bool(rank1_context) and SW.RANK1_CTX
+        # (share, runs) -> the plan, its closures and its captured graph.  The model owns the plans: it keeps at most
+        # MAX_LIVE_PLANS of them and tells this loop which ones it let go (plan_dropped), so no entry outlives its plan there —
+        # the stage-2 autoregression walks four seen-frame patterns, i.e. four entries, per call
         self._variants = {}
         self._v = None
+        if hasattr(unet, "watch_plans"):
+            unet.watch_plans(self)
+
+    def plan_dropped(self, prog):
+        """The model evicted `prog` (its LRU bound, or new weights): forget the variant built around it, graph included.  The
+        variant selected by the last load() stays usable until the next one — it is in use, not merely kept."""
+        for key in [k for k, v in self._variants.items() if v["prog"] is prog]:
+            del self._variants[key]
 
     def _select(self, share, runs=None):
         """share: the shared-CFG-prefix plan; runs: the full-rank image runs of the context (engine.full_rank_runs) when some
         images' context rows are all equal — the rank-1-context plan — else None."""
+        # keyed by the runs the plan really uses (None where the rank-1 form is declined), as the model keys its own cache
+        b = self.S * (1 if self.split is not None else self.reps)
+        runs = plan_rank1_runs(runs, b * self.f, self.ctx_len) if SW.RANK1_CTX else None
         v = self._variants.get((share, runs))
+        if v is not None:
+            # also marks the plan as the model's most recently used one
+            kept = self.unet.program(b, self.f, self.H, self.W, self.ctx_len, shared_prefix=share and self.split is None,
+                                     rank1_runs=runs)
+            if kept is not v["prog"]:       # not the model's plan for this key any more: build on the one it has now
+                del self._variants[(share, runs)]
+                v = None
         if v is None:
             S, R, f, H, W = self.S, self.reps, self.f, self.H, self.W
             if self.split is not None:

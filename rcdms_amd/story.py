@@ -7,7 +7,8 @@ stage2_batchtest_rcdms_model.py reads them back — one story per pipeline call.
   * `write_stage1_embeds`, the files of stage1…:260,264 for a stage-2 process of the old kind;
   * `StoryRunner`: uint8 frames + captions -> CLIP vision forward -> stage 1 -> cosine figure -> hand-off -> stage 2,
     batched over S, all tensors staying on the device; on request the per-frame SSIM / PSNR / CLIP-I of the generated frames
-    against their targets (rcdms_amd.metrics).
+    against their targets (rcdms_amd.metrics); on request stage 2's autoregression — five passes at batch S, the kept
+    frames handed on as device bytes (`source_from_bytes`) — and the stage-2 driver's PNG files (`write_story_pngs`).
 The hot paths are the two captured loops (rcdms_amd.sampler) at batch S; this module is glue around them."""
 import os
 from dataclasses import dataclass
@@ -99,9 +100,51 @@ class StoryResult:
     ssim: Optional[torch.Tensor] = None    # (S, 5) float64, generated frame against its resized target (metrics=("ssim",))
     psnr: Optional[torch.Tensor] = None    # (S, 5) float64, inf for identical frames (metrics=("psnr",))
     clip_i: Optional[torch.Tensor] = None  # (S, 5) cosine of the generated frames' CLIP embeddings and target_embeds ("clip_i")
+    frames_u8: Optional[torch.Tensor] = None   # (S, 5, H, W, 3) device uint8: the kept frames a stage-2 autoregressive run handed on
 
 
 METRICS = ("ssim", "psnr", "clip_i")
+AUTOREG_OUTPUTS = ("tensor", "uint8", "png")
+
+
+def source_from_bytes(frames_u8):
+    """uint8 frames (..., H, W, 3) -> fp32 (..., 3, H, W) in [-1, 1]: what the driver's reg_augment (ToTensor, then
+    Normalize([0.5], [0.5]), no resize) makes of a PNG file it wrote from those bytes (stage2…:306-343) — (b / 255 - 0.5) / 0.5
+    element by element, on the frames' device.  The 256 values are computed once on the host, where `/ 255` is the IEEE
+    division ToTensor makes (a device kernel may multiply by a rounded 1 / 255 instead), and looked up by byte there."""
+    table = _SOURCE_VALUES.get(frames_u8.device)
+    if table is None:
+        table = ((torch.arange(256, dtype=torch.float32) / 255 - 0.5) / 0.5).to(frames_u8.device)
+        _SOURCE_VALUES[frames_u8.device] = table
+    return table[frames_u8.to(torch.int32)].movedim(-1, -3)
+
+
+_SOURCE_VALUES = {}
+
+
+def write_story_pngs(frames_dir, grid_dir, indices, frames_u8, targets_u8=None, files=None):
+    """The stage-2 driver's files for S stories, encoded on the device (image.encode_png, checkpoint.story_grid_png):
+    frames_dir: `{index}_{i}.png`, frame i of story `index` (stage2…:362,384); grid_dir: `{index}.png`, the 2 x 5 grid of the
+    five generated frames over the five targets (:389-401).  frames_u8 / targets_u8: device uint8 (S, 5, H, W, 3); files:
+    the S x 5 frame files where the caller has encoded them already.  A directory that is None is skipped.  -> the files."""
+    S = frames_u8.shape[0]
+    if frames_dir is not None:
+        if files is None:
+            from .image import encode_png
+            flat = encode_png(frames_u8.reshape(S * FRAMES, *frames_u8.shape[2:]))
+            files = [flat[s * FRAMES:(s + 1) * FRAMES] for s in range(S)]
+        os.makedirs(frames_dir, exist_ok=True)
+        for s, index in enumerate(indices):
+            for i in range(FRAMES):
+                with open(os.path.join(frames_dir, f"{index}_{i}.png"), "wb") as f:
+                    f.write(files[s][i])
+    if grid_dir is not None:
+        from .checkpoint import story_grid_png
+        os.makedirs(grid_dir, exist_ok=True)
+        for s, index in enumerate(indices):
+            with open(os.path.join(grid_dir, f"{index}.png"), "wb") as f:
+                f.write(story_grid_png([*frames_u8[s], *targets_u8[s]], 2, FRAMES))
+    return files
 
 
 class StoryRunner:
@@ -162,7 +205,8 @@ class StoryRunner:
     @torch.no_grad()
     def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
-                 save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=()):
+                 save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=(),
+                 stage2_autoreg=False, frames_dir=None, grid_dir=None):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
@@ -170,7 +214,24 @@ class StoryRunner:
         metrics: any of "ssim", "psnr", "clip_i" — per-frame figures of the generated frames against the five given frames
         resized to the stage-2 size with Pillow's bilinear filter (the driver's vis_augment, stage2…:390-396), in the result's
         fields of those names, computed on the device (rcdms_amd.metrics; "clip_i" is one more vision forward).  They need a
-        stage-2 run with output_type="uint8".  metrics=(): nothing more is launched."""
+        stage-2 run with output_type="uint8".  metrics=(): nothing more is launched.
+        stage2_autoreg: the stage-2 driver's --autoreg loop (stage2…:304-362) for the S stories, independent of `autoreg`
+        (stage 1's loop): five stage-2 calls at batch S, pass i keeping frame i of every story —
+          pass 0: the call of stage2_autoreg=False (given frame 0 seen, image_embeds_1 its hidden state, proj_embeds_0
+                  embeds[1:]);
+          pass i >= 1: the generated frames 0..i-1 seen — frame 0 too: the given one is replaced (:306-311) —, as
+                  source_from_bytes of the bytes kept, no file in between; image_embeds_1 the vision tower's hidden states
+                  of those i frames (the reference's call omits both embeddings and cannot run: they follow the frames in
+                  source_img here, so that the fine stack sees what the VAE sees; each kept frame is encoded once);
+                  proj_embeds_0 embeds[i:].
+        Every pass takes this call's guidance_scale, num_inference_steps, fix_context_order, guidance_rescale and eta, and
+        the same `generator` object(s): with one generator per story, story s's five passes draw from it one after the other
+        (posterior noise, initial latents, per-step noise; then the next pass) as the driver's five calls do; one generator
+        for S > 1 stories serves them pass-major — all stories of pass 0, then of pass 1 … — which no sequence of
+        single-story runs reproduces.  `videos` holds frame i of pass i in the layout of output_type ("tensor", "uint8" or
+        "png"), `frames_u8` the kept bytes; metrics are computed from those bytes whatever the output_type.
+        frames_dir / grid_dir (any stage-2 run with one of those three output types): the driver's `{index}_{i}.png` per
+        generated frame and `{index}.png`, the generated frames over the resized targets (write_story_pngs)."""
         metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
         for m in metrics:
             if m not in METRICS:
@@ -186,7 +247,18 @@ class StoryRunner:
             raise ValueError("stage 2 asked for, but the runner was built without a stage-2 pipeline")
         if metrics and not stage2:
             raise ValueError(f"metrics {metrics} compare the frames stage 2 generates with their targets: this call runs no stage 2")
-        if metrics and output_type != "uint8":
+        if stage2_autoreg and not stage2:
+            raise ValueError("stage2_autoreg=True repeats stage 2 five times: this call runs no stage 2")
+        if stage2_autoreg and output_type not in AUTOREG_OUTPUTS:
+            raise ValueError(f"stage2_autoreg=True hands uint8 frames from pass to pass: output_type is one of {AUTOREG_OUTPUTS}, "
+                             f"not {output_type!r}")
+        files_asked = frames_dir is not None or grid_dir is not None
+        if files_asked and not stage2:
+            raise ValueError("frames_dir / grid_dir hold the frames stage 2 generates: this call runs no stage 2")
+        if files_asked and output_type not in AUTOREG_OUTPUTS:
+            raise ValueError(f"frames_dir / grid_dir are written from uint8 frames: output_type is one of {AUTOREG_OUTPUTS}, "
+                             f"not {output_type!r}")
+        if metrics and output_type != "uint8" and not stage2_autoreg:
             raise ValueError(f"metrics {metrics} are computed on uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
         frames = torch.as_tensor(frames)
         if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[1] != FRAMES or frames.shape[-1] != 3:
@@ -224,7 +296,7 @@ class StoryRunner:
         if save_dir is not None:
             for s, index in enumerate(indices):
                 write_stage1_embeds(save_dir, index, embeds[s])
-        videos = None
+        videos = frames_u8 = None
         if stage2:
             pipe, ft = self.stage2_pipe, self.frame_transform
             H, W = ft.height, ft.width
@@ -234,13 +306,62 @@ class StoryRunner:
             label = torch.zeros(S, FRAMES, h, w, dtype=torch.float32, device=self.device)
             label[:, 0] = 1.0
             hidden = vis.last_hidden_state.reshape(S, FRAMES, *vis.last_hidden_state.shape[1:])
-            videos = pipe(prompt=texts, source_img=source, image_embeds_1=[hidden[s, :1] for s in range(S)],
-                          proj_embeds_0=[embeds[s, 1:].unsqueeze(1) for s in range(S)], mask_label=label,
-                          video_length=FRAMES, height=H, width=W, guidance_scale=guidance_scale, generator=generator,
-                          num_inference_steps=num_inference_steps, output_type=output_type,
-                          fix_context_order=fix_context_order, guidance_rescale=guidance_rescale, eta=eta).videos
-        figures = self.story_metrics(videos, frames, target, metrics) if metrics else {}
-        return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures)
+            kw = dict(prompt=texts, video_length=FRAMES, height=H, width=W, guidance_scale=guidance_scale, generator=generator,
+                      num_inference_steps=num_inference_steps, fix_context_order=fix_context_order,
+                      guidance_rescale=guidance_rescale, eta=eta)
+            img1, proj0 = [hidden[s, :1] for s in range(S)], [embeds[s, 1:].unsqueeze(1) for s in range(S)]
+            if stage2_autoreg:
+                videos, frames_u8 = self._stage2_autoreg(source, label, img1, embeds, output_type, kw)
+            elif files_asked:
+                videos, frames_u8 = self._stage2_bytes(source, label, img1, proj0, output_type, kw)
+            else:
+                videos = pipe(source_img=source, image_embeds_1=img1, proj_embeds_0=proj0, mask_label=label,
+                              output_type=output_type, **kw).videos
+            files = None
+            if frames_u8 is not None and output_type == "png":
+                from .image import encode_png
+                flat = encode_png(frames_u8.reshape(S * FRAMES, *frames_u8.shape[2:]))
+                videos = files = [flat[s * FRAMES:(s + 1) * FRAMES] for s in range(S)]
+            if files_asked:
+                write_story_pngs(frames_dir, grid_dir, indices, frames_u8,
+                                 self.target_frames(frames) if grid_dir is not None else None, files)
+        figures = {}
+        if metrics:
+            figures = self.story_metrics(frames_u8 if stage2_autoreg else videos, frames, target, metrics)
+        return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures,
+                           frames_u8=frames_u8 if stage2_autoreg else None)
+
+    def _stage2_bytes(self, source, label, img1, proj0, output_type, kw):
+        """One stage-2 call whose frames are also wanted as bytes -> (videos, device uint8 (S, 5, H, W, 3)).  "tensor": the
+        float frames and the bytes of the same decode; "uint8" / "png": the bytes (the caller encodes the files)."""
+        if output_type == "tensor":
+            out = self.stage2_pipe(source_img=source, image_embeds_1=img1, proj_embeds_0=proj0, mask_label=label,
+                                   output_type="tensor", return_uint8=True, **kw)
+            return out.videos, out.frames_u8
+        u8 = self.stage2_pipe(source_img=source, image_embeds_1=img1, proj_embeds_0=proj0, mask_label=label,
+                              output_type="uint8", **kw).videos
+        return u8, u8
+
+    def _stage2_autoreg(self, source, label, img1, embeds, output_type, kw):
+        """The five passes.  source / label / img1: pass 0's, i.e. the plain call's; embeds (S, 5, E).  -> (videos in the
+        layout of "tensor" or "uint8", the kept bytes (S, 5, H, W, 3)); everything handed on stays on the device."""
+        S = source.shape[0]
+        source, label = source.clone(), label.clone()
+        kept_u8, kept_video, seen_hidden = [], [], []
+        for i in range(FRAMES):
+            if i >= 1:
+                new = kept_u8[i - 1]                                                # (S, H, W, 3), kept by the pass before
+                source[:, i - 1] = source_from_bytes(new)                           # pass 1: replaces the given frame 0
+                label[:, i - 1] = 1.0
+                seen_hidden.append(self.image_encoder(self._pixels(new)).last_hidden_state)   # (S, tokens, width), once per frame
+                img1 = [torch.stack([hs[s] for hs in seen_hidden]) for s in range(S)]
+            proj0 = [embeds[s, max(i, 1):].unsqueeze(1) for s in range(S)]
+            videos, u8 = self._stage2_bytes(source, label, img1, proj0, output_type, kw)
+            kept_u8.append(u8[:, i].contiguous())
+            if output_type == "tensor":
+                kept_video.append(videos[:, :, i])
+        frames_u8 = torch.stack(kept_u8, dim=1)
+        return (torch.stack(kept_video, dim=2) if output_type == "tensor" else frames_u8), frames_u8
 
     def target_frames(self, frames):
         """The five given frames of every story at the stage-2 size, uint8 (S, 5, H, W, 3): Pillow's bilinear resize as bytes,

@@ -17,6 +17,19 @@ CIN_PAD = 64   # conv_in reads its 9 channels from a 64-wide zero-padded row (on
 COUT_PAD = 8   # conv_out writes 4 channels + 4 zero columns (16-byte rows)
 
 
+def plan_rank1_runs(rank1_runs, images, L):
+    """The `rank1_runs` a UNetProgram over `images` = b * frames images and L context rows ends up with for the ones asked
+    for: None when the rank-1 form is declined (nothing asked, every image full rank, or a context too long for rcdm_xattn),
+    else the runs as a tuple of int pairs.  The one place that decides it: UNet3DConditionModel.program and
+    DenoiseLoop key their caches with it, so that two requests for the same plan are one entry."""
+    if rank1_runs is None:
+        return None
+    runs = tuple((int(i0), int(i1)) for i0, i1 in rank1_runs)
+    if sum(i1 - i0 for i0, i1 in runs) < images and 0 < L <= XATTN_MAX_KEYS:
+        return runs
+    return None
+
+
 class UNetProgram:
     """Static launch plan of one UNet3DConditionModel.forward for fixed (b, f, H, W, L)."""
 
@@ -34,8 +47,7 @@ class UNetProgram:
             runs = tuple((int(i0), int(i1)) for i0, i1 in rank1_runs)
             if any(not (0 <= i0 < i1 <= b * frames) for i0, i1 in runs) or any(a[1] >= c[0] for a, c in zip(runs, runs[1:])):
                 raise hip.RcdmError(f"rank1_runs {runs}: not disjoint ascending runs of the {b * frames} images")
-            if sum(i1 - i0 for i0, i1 in runs) < b * frames and 0 < L <= XATTN_MAX_KEYS:
-                self.rank1_runs = runs      # (every image full rank, or a context too long for rcdm_xattn: the general plan)
+            self.rank1_runs = plan_rank1_runs(runs, b * frames, L)   # (None: the general plan)
         if shared_prefix and (b % 2 or cfg["down_block_types"][0] != "CrossAttnDownBlock3D"):
             raise hip.RcdmError("shared_prefix needs an even batch and a cross-attention first block")
         self.shared_prefix = bool(shared_prefix)

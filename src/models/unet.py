@@ -8,6 +8,7 @@ launches (captured into a hipGraph after the first call).  There is no torch fal
 import inspect
 import json
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Optional, Tuple, Union
 
@@ -231,8 +232,22 @@ class UNet3DConditionModel(nn.Module):
     MAX_LIVE_PLANS = 4   # plans (geometry x shared-prefix x rank-1-context variant) kept packed at once (2.55 GB of f16 weights + ~3.5 GB of buffers each)
 
     def _invalidate(self):
+        for prog in getattr(self, "_programs", {}).values():
+            self._dropped(prog)
         self._programs = {}
         self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
+    def watch_plans(self, user):
+        """Register `user` (held weakly; rcdms_amd.sampler.DenoiseLoop): `user.plan_dropped(prog)` is called for every plan
+        this model lets go of, so that whatever the user built around it (closures, a captured graph) goes with it and the
+        model's bound MAX_LIVE_PLANS is the bound on live plans."""
+        if getattr(self, "_plan_users", None) is None:
+            self._plan_users = weakref.WeakSet()
+        self._plan_users.add(user)
+
+    def _dropped(self, prog):
+        for user in list(getattr(self, "_plan_users", None) or ()):
+            user.plan_dropped(prog)
 
     def load_state_dict(self, *args, **kwargs):
         self._invalidate()
@@ -267,13 +282,14 @@ class UNet3DConditionModel(nn.Module):
                                 "(rcdms_amd has no CPU fallback)")
         if self.config.motion_module_decoder_only and self.config.use_motion_module:
             raise NotImplementedError("motion_module_decoder_only is not supported on the HIP path")
-        if rank1_runs is not None and (sum(i1 - i0 for i0, i1 in rank1_runs) >= b * frames or not engine.SW.RANK1_CTX):
-            rank1_runs = None       # every image full rank (or the fast path switched off): the general plan
-        key = (b, frames, H, W, L, str(dev), bool(shared_prefix), tuple(rank1_runs) if rank1_runs is not None else None)
+        # the runs the plan will really use (None: every image full rank, a context too long for the rank-1 form, or the fast
+        # path switched off — the general plan): requests that end in the same plan share one entry
+        rank1_runs = engine.plan_rank1_runs(rank1_runs, b * frames, L) if engine.SW.RANK1_CTX else None
+        key = (b, frames, H, W, L, str(dev), bool(shared_prefix), rank1_runs)
         prog = self._programs.get(key)
         if prog is None:
             while len(self._programs) >= self.MAX_LIVE_PLANS:      # least recently used geometry goes first
-                self._programs.pop(next(iter(self._programs)))
+                self._dropped(self._programs.pop(next(iter(self._programs))))
             with torch.no_grad():
                 prog = engine.UNetProgram(self.engine_config(), self.state_dict(), b, frames, H, W, L, dev,
                                           shared_prefix=shared_prefix, rank1_runs=rank1_runs)

@@ -44,6 +44,7 @@ class local_feature(nn.Module):
 @dataclass
 class RCDMsPipelineOutput:
     videos: Union[torch.Tensor, np.ndarray]
+    frames_u8: Optional[torch.Tensor] = None   # return_uint8=True: the bytes of `videos`, device uint8 (b, f, H, W, 3)
 
 
 def _force_config(obj, key, value):
@@ -201,8 +202,9 @@ class RCDMsPipeline:
             return [x]
         return [x[i:i + per] for i in range(0, n, per)]
 
-    def decode_latents(self, latents):
-        """(:274-287) one frame at a time through the user's VAE."""
+    def decode_latents(self, latents, with_uint8=False):
+        """(:274-287) one frame at a time through the user's VAE.  with_uint8: -> (video, bytes) — the same decode also
+        truncated to bytes on the device (rcdms_amd.image.frames_to_uint8), uint8 (b, f, H, W, 3)."""
         f = latents.shape[2]
         latents = (1 / 0.18215 * latents).permute(0, 2, 1, 3, 4).reshape(-1, latents.shape[1], *latents.shape[3:])
         if self.vae_decoder is not None:
@@ -211,7 +213,11 @@ class RCDMsPipeline:
             frames = [self.vae.decode(latents[i:i + 1]).sample for i in range(latents.shape[0])]
             video = torch.cat(frames)
         video = video.reshape(-1, f, *video.shape[1:]).permute(0, 2, 1, 3, 4)
-        return (video / 2 + 0.5).clamp(0, 1).cpu().float().numpy()
+        out = (video / 2 + 0.5).clamp(0, 1).cpu().float().numpy()
+        if with_uint8:
+            from rcdms_amd.image import frames_to_uint8
+            return out, frames_to_uint8(video)
+        return out
 
     def decode_latents_uint8(self, latents):
         """output_type="uint8": the frames of decode_latents truncated to bytes — trunc(clamp(x / 2 + 0.5, 0, 1) * 255), the
@@ -283,10 +289,13 @@ class RCDMsPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "tensor", return_dict: bool = True,
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: Optional[int] = 1,
-                 fix_context_order: bool = False, png_match: bool = False, guidance_rescale: float = 0.0, **kwargs):
+                 fix_context_order: bool = False, png_match: bool = False, guidance_rescale: float = 0.0,
+                 return_uint8: bool = False, **kwargs):
         """guidance_rescale (what the reference driver passes, stage2_batchtest_rcdms_model.py:352): Lin et al. 2023 §3.4 on
         the guided noise prediction, inside the captured step; 0 is off.  eta: stochastic DDIM with a DDIMScheduler (the
-        per-step noise from `generator`), ignored by every other scheduler type (prepare_extra_step_kwargs, :289-298)."""
+        per-step noise from `generator`), ignored by every other scheduler type (prepare_extra_step_kwargs, :289-298).
+        return_uint8: with the float output types, also `frames_u8` in the result — the same decode truncated to bytes on the
+        device, what output_type="uint8" holds (the frames the stage-2 autoregression hands to its next pass)."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -296,7 +305,7 @@ class RCDMsPipeline:
             return self._call_stories(prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
                                       num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator,
                                       latents, output_type, return_dict, callback, callback_steps, fix_context_order,
-                                      png_match, guidance_rescale, eta)
+                                      png_match, guidance_rescale, eta, return_uint8)
         batch_size = 1
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -329,11 +338,11 @@ class RCDMsPipeline:
 
         return self._sample_and_decode(latents, mask5, masked_latents, context, text_embeddings.dtype, num_inference_steps,
                                        guidance_scale, generator, None, callback, callback_steps, output_type, return_dict,
-                                       png_match, guidance_rescale, eta)
+                                       png_match, guidance_rescale, eta, return_uint8)
 
     def _sample_and_decode(self, latents, mask5, masked_latents, context, dtype, num_inference_steps, guidance_scale,
                            generator, noise, callback, callback_steps, output_type, return_dict, png_match,
-                           guidance_rescale=0.0, eta=0.0):
+                           guidance_rescale=0.0, eta=0.0, return_uint8=False):
         """The captured loop on the staged inputs, then the VAE decode by `output_type` (:455-513); the batch axis of
         `latents` is the story axis."""
         with self.progress_bar(total=num_inference_steps) as bar:
@@ -357,17 +366,21 @@ class RCDMsPipeline:
                 files = encode_png(video.reshape(b * f, *video.shape[2:]), match=png_match)
                 video = [files[i * f:(i + 1) * f] for i in range(b)]
             return RCDMsPipelineOutput(videos=video) if return_dict else video
-        video = self.decode_latents(final.to(dtype))
+        frames_u8 = None
+        if return_uint8:
+            video, frames_u8 = self.decode_latents(final.to(dtype), with_uint8=True)
+        else:
+            video = self.decode_latents(final.to(dtype))
         if output_type == "tensor":
             video = torch.from_numpy(video)
         if not return_dict:
-            return video
-        return RCDMsPipelineOutput(videos=video)
+            return (video, frames_u8) if return_uint8 else video
+        return RCDMsPipelineOutput(videos=video, frames_u8=frames_u8)
 
     def _call_stories(self, prompt, source_img, image_embeds_1, proj_embeds_0, mask_label, height, width,
                       num_inference_steps, guidance_scale, negative_prompt, num_videos_per_prompt, generator, latents,
                       output_type, return_dict, callback, callback_steps, fix_context_order, png_match,
-                      guidance_rescale=0.0, eta=0.0):
+                      guidance_rescale=0.0, eta=0.0, return_uint8=False):
         """`prompt` is S lists of five captions: S stories through one captured loop.  Story s is the single-story call on
         story s's inputs with story s's generator (one generator: the S calls made one after the other with it).  Every
         story's ten context rows and mask rows are built as in that call and then placed at the loop's batch rows r * S + s
@@ -445,7 +458,7 @@ class RCDMsPipeline:
         noise = torch.cat(noise, dim=1) if need_noise else None         # (T, S, 4, 5, h, w)
         return self._sample_and_decode(torch.cat(lat), mask5, masked_latents, context, dt, num_inference_steps,
                                        guidance_scale, None, noise, callback, callback_steps, output_type, return_dict,
-                                       png_match, guidance_rescale, eta)
+                                       png_match, guidance_rescale, eta, return_uint8)
 
 
 # stage2_batchtest_rcdms_model.py:30 imports RCDMsPipeline but :246 instantiates AnimationPipeline
