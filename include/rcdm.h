@@ -934,6 +934,68 @@ int rcdm_frame_metrics(const rcdm_metrics_desc* d, const void* a, const void* b,
                        int64_t* sad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fréchet distance: running float64 statistics of feature rows on the device, and the distance
+ *   |mu_a - mu_b|^2 + tr S_a + tr S_b - 2 tr (S_a S_b)^(1/2)
+ * between two sets of them (FID when the rows are Inception pool features; here the CLIP image embeddings the story runner
+ * already holds, a "CLIP-FD").  The reference drivers compute no set-level figure.  tr (S_a S_b)^(1/2) is the sum of the
+ * singular values of F_b^T F_a for factors S = F F^T; both the factors and the singular values come from one-sided (Hestenes)
+ * Jacobi on the rows of a buffer (csrc/frechet_core.h: pairing, rotation, rules 1-3).  No matrix square root is taken and no
+ * matrix is squared.  Every sum has a fixed order and nothing but the rotation counter is atomic: the same inputs give the
+ * same bits.  All buffers are on the device; float64 pointers are 8-byte aligned.  1 <= d <= 4096.
+ *   rcdm_feature_stats_update    x: n rows of d features, RCDM_FSTATS_F32 or _F16, ld elements between rows (columns d..ld are
+ *                                never read); shift: float32[d], the point the sums are taken about.  sum[d] += sum_r (x_r - k),
+ *                                outer[d][d] (dense) += sum_r (x_r - k)(x_r - k)^T, operands widened to float64 before the
+ *                                subtraction, the outer product on the float64 matrix pipe.  Two launches.  The column sums
+ *                                are one thread per column over all n rows (d / 256 workgroups, a chain of n additions):
+ *                                measured at n = 1000 only; a caller with millions of rows should pass them in chunks.
+ *   rcdm_gemm_tn_f64             c[m][n] = a^T b for a[k][m], b[k][n], float64 (the same kernel, on doubles, without a shift).
+ *   rcdm_feature_stats_finalize  mean[d] = k + sum / n; with cov != null (n >= 2): cov[d][d] = (outer - sum sum^T / n) / (n - 1),
+ *                                both triangles written from the upper one of `outer`, and trace[0] = tr cov.
+ *   rcdm_frechet_trace           out[0] = the trace of a dense d x d matrix;  rcdm_frechet_mean_term  out[0] = |mu_a - mu_b|^2.
+ *   rcdm_jacobi_sweep            one sweep over w: `rows` vectors (even; an odd dimension is padded with one zero vector) of
+ *                                `len` doubles, ld doubles apart; dim: the dimension the thresholds of rules 2 and 3 use.
+ *                                rows + 1 launches: the norms, the sweep's threshold, and one launch per round of rows / 2
+ *                                disjoint pairs.  *count (int32) is zeroed and then holds the rotations of the sweep: the caller
+ *                                reads it back and stops at 0.  No launch waits on another workgroup.
+ *   rcdm_jacobi_norm_sum         out[0] = the sum of the vectors' norms (after the last sweep: of the singular values),
+ *                                out[1] = the largest.
+ *   rcdm_frechet_factor          len == dim: after the last sweep over a covariance, vector j is lambda_j v_j.  f[len][ldf >= rows]
+ *                                gets column j = w_j / sqrt(lambda_j), or zeros where lambda_j <= dim 2^-52 lambda_max (rule 3);
+ *                                *rank (int32) = the columns kept.  f^T f' is then rcdm_gemm_tn_f64's to form.
+ *   rcdm_jacobi_workspace_bytes  (4 + rows) doubles, shared by the three entry points above (0 for a refused descriptor).
+ * RCDM_EINVAL: null pointers, n or d < 1, ld < d (len, rows, the GEMM's sizes), an unknown dtype, odd rows, a misaligned
+ * pointer, cov with n < 2.  RCDM_ESHAPE: d, rows, len or dim above 4096, n above 2^30.  RCDM_EWORKSPACE: workspace null or short.
+ * All checked before anything is launched; no allocation.
+ * ---------------------------------------------------------------------------------------------- */
+#define RCDM_FSTATS_F32 0
+#define RCDM_FSTATS_F16 1
+typedef struct {
+  int64_t ld;                      /* elements between rows of x, >= d */
+  int32_t n, d;
+  int32_t dtype;                   /* RCDM_FSTATS_* */
+  int32_t reserved;
+} rcdm_fstats_desc;
+typedef struct {
+  int64_t ld;                      /* doubles between vectors, >= len */
+  int32_t rows, len, dim;
+  int32_t reserved;
+} rcdm_jacobi_desc;
+int rcdm_feature_stats_update(const rcdm_fstats_desc* d, const void* x, const float* shift, double* sum, double* outer,
+                              void* stream);
+int rcdm_gemm_tn_f64(int32_t m, int32_t n, int32_t k, const double* a, int64_t lda, const double* b, int64_t ldb, double* c,
+                     int64_t ldc, void* stream);
+int rcdm_feature_stats_finalize(int32_t d, int64_t n, const float* shift, const double* sum, const double* outer, double* mean,
+                                double* cov, double* trace, void* stream);
+int rcdm_frechet_trace(int32_t d, const double* a, double* out, void* stream);
+int rcdm_frechet_mean_term(int32_t d, const double* mu_a, const double* mu_b, double* out, void* stream);
+size_t rcdm_jacobi_workspace_bytes(const rcdm_jacobi_desc* d);
+int rcdm_jacobi_sweep(const rcdm_jacobi_desc* d, double* w, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int rcdm_jacobi_norm_sum(const rcdm_jacobi_desc* d, const double* w, double* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int rcdm_frechet_factor(const rcdm_jacobi_desc* d, const double* w, double* f, int64_t ldf, int32_t* rank, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
  * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
  * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the

@@ -116,6 +116,14 @@ class MetricsDesc(C.Structure):
                 ("sample_covariance", C.c_int32)]
 
 
+class FStatsDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("n", C.c_int32), ("d", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JacobiDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("rows", C.c_int32), ("len", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TokAdded(C.Structure):
     _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
 
@@ -127,6 +135,8 @@ class TokenizeDesc(C.Structure):
 
 
 TOK_MAX_CAPTION, TOK_MAX_ADDED, TOK_MAX_ROWS, TOK_MAX_ADDED_LEN, TOK_MAX_RANK, TOK_MAX_CAPTIONS = 1024, 64, 66, 32, 1 << 22, 1 << 20
+FSTATS_F32, FSTATS_F16 = 0, 1                            # FStatsDesc.dtype
+FRECHET_MAX_DIM = 4096
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
 PNG_RGB, PNG_BGR = 0, 1
@@ -218,6 +228,15 @@ SYMBOLS = {
     "rcdm_png_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rcdm_frame_metrics_workspace_bytes": (_SZ, [C.POINTER(MetricsDesc)]),
     "rcdm_frame_metrics": (C.c_int, [C.POINTER(MetricsDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_feature_stats_update": (C.c_int, [C.POINTER(FStatsDesc), _P, _P, _P, _P, _P]),
+    "rcdm_gemm_tn_f64": (C.c_int, [_I, _I, _I, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P]),
+    "rcdm_feature_stats_finalize": (C.c_int, [_I, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "rcdm_frechet_trace": (C.c_int, [_I, _P, _P, _P]),
+    "rcdm_frechet_mean_term": (C.c_int, [_I, _P, _P, _P, _P]),
+    "rcdm_jacobi_workspace_bytes": (_SZ, [C.POINTER(JacobiDesc)]),
+    "rcdm_jacobi_sweep": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, _P, _SZ, _P]),
+    "rcdm_jacobi_norm_sum": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, _P, _SZ, _P]),
+    "rcdm_frechet_factor": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, C.c_int64, _P, _P, _SZ, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -594,6 +613,46 @@ def clip_tokenize(desc, text, offsets, byte_ids, added, pairs, input_ids, attent
     _check(load().rcdm_clip_tokenize(C.byref(desc), text, offsets, byte_ids, added, pairs, input_ids, attention_mask, lengths,
                                      pool_index, workspace, workspace_bytes, stream_ptr() if stream is None else stream),
            "rcdm_clip_tokenize")
+
+
+def _st(stream):
+    return stream_ptr() if stream is None else stream
+
+
+def feature_stats_update(desc, x, shift, sum_, outer, stream=None):
+    _check(load().rcdm_feature_stats_update(C.byref(desc), x, shift, sum_, outer, _st(stream)), "rcdm_feature_stats_update")
+
+
+def gemm_tn_f64(m, n, k, a, lda, b, ldb, c, ldc, stream=None):
+    _check(load().rcdm_gemm_tn_f64(m, n, k, a, lda, b, ldb, c, ldc, _st(stream)), "rcdm_gemm_tn_f64")
+
+
+def feature_stats_finalize(d, n, shift, sum_, outer, mean, cov, trace, stream=None):
+    _check(load().rcdm_feature_stats_finalize(d, n, shift, sum_, outer, mean, cov, trace, _st(stream)), "rcdm_feature_stats_finalize")
+
+
+def frechet_trace(d, a, out, stream=None):
+    _check(load().rcdm_frechet_trace(d, a, out, _st(stream)), "rcdm_frechet_trace")
+
+
+def frechet_mean_term(d, mu_a, mu_b, out, stream=None):
+    _check(load().rcdm_frechet_mean_term(d, mu_a, mu_b, out, _st(stream)), "rcdm_frechet_mean_term")
+
+
+def jacobi_workspace_bytes(desc):
+    return int(load().rcdm_jacobi_workspace_bytes(C.byref(desc)))
+
+
+def jacobi_sweep(desc, w, count, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_jacobi_sweep(C.byref(desc), w, count, workspace, workspace_bytes, _st(stream)), "rcdm_jacobi_sweep")
+
+
+def jacobi_norm_sum(desc, w, out, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_jacobi_norm_sum(C.byref(desc), w, out, workspace, workspace_bytes, _st(stream)), "rcdm_jacobi_norm_sum")
+
+
+def frechet_factor(desc, w, f, ldf, rank, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_frechet_factor(C.byref(desc), w, f, ldf, rank, workspace, workspace_bytes, _st(stream)), "rcdm_frechet_factor")
 
 
 def frame_metrics_workspace_bytes(desc):
