@@ -963,6 +963,15 @@ int rcdm_frame_metrics(const rcdm_metrics_desc* d, const void* a, const void* b,
  *                                gets column j = w_j / sqrt(lambda_j), or zeros where lambda_j <= dim 2^-52 lambda_max (rule 3);
  *                                *rank (int32) = the columns kept.  f^T f' is then rcdm_gemm_tn_f64's to form.
  *   rcdm_jacobi_workspace_bytes  (4 + rows) doubles, shared by the three entry points above (0 for a refused descriptor).
+ *   rcdm_cholesky_pivoted_f64    the other way to a factor: a[d][ld], dense and symmetric, is left intact; f[d][ldf] gets column
+ *                                j = column j of P L of the diagonally pivoted Cholesky factorisation, rows in the original
+ *                                order, zero columns from the rank on; *rank (int32) = the steps taken.  Step j takes the
+ *                                largest remaining diagonal (lowest index on a tie) and stops when it is not above d 2^-52 x the
+ *                                largest diagonal of a (zero, negative and NaN diagonals stop it the same way).  Blocked and
+ *                                right-looking in panels of nb columns (16, 32, 64 or 128; 0: the library's choice, 16): 1 + 2 d +
+ *                                (d - 1) / nb launches, the trailing update on the float64 matrix pipe, no read-back, no
+ *                                atomics.  Columns d..ld of a and d..ldf of f are neither read nor written.
+ *   rcdm_cholesky_workspace_bytes  8 + d d + nb d + 2 d doubles and 2 (d rounded up to even) int32 (0 for a refused descriptor).
  * RCDM_EINVAL: null pointers, n or d < 1, ld < d (len, rows, the GEMM's sizes), an unknown dtype, odd rows, a misaligned
  * pointer, cov with n < 2.  RCDM_ESHAPE: d, rows, len or dim above 4096, n above 2^30.  RCDM_EWORKSPACE: workspace null or short.
  * All checked before anything is launched; no allocation.
@@ -994,6 +1003,15 @@ int rcdm_jacobi_norm_sum(const rcdm_jacobi_desc* d, const double* w, double* out
                          void* stream);
 int rcdm_frechet_factor(const rcdm_jacobi_desc* d, const double* w, double* f, int64_t ldf, int32_t* rank, void* workspace,
                         size_t workspace_bytes, void* stream);
+typedef struct {
+  int64_t ld;                      /* doubles between rows of a, >= d */
+  int64_t ldf;                     /* doubles between rows of f, >= d */
+  int32_t d;
+  int32_t nb;                      /* panel width: 16, 32, 64, 128, or 0 for the library's choice */
+} rcdm_cholesky_desc;
+size_t rcdm_cholesky_workspace_bytes(const rcdm_cholesky_desc* d);
+int rcdm_cholesky_pivoted_f64(const rcdm_cholesky_desc* d, const double* a, double* f, int32_t* rank, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",

@@ -9,6 +9,10 @@
 //                                rotations, one launch per round, one workgroup per pair.  No workgroup waits on another.
 //   rcdm_jacobi_norm_sum         the row norms, their sum and their maximum.
 //   rcdm_frechet_factor          rows w_j = lambda_j v_j of a finished sweep -> the factor F (columns w_j / sqrt(lambda_j)).
+//   rcdm_cholesky_pivoted_f64    the other way to a factor: columns of P L of the diagonally pivoted Cholesky factorisation, blocked and
+//                                right-looking.  Per column one single-workgroup launch (the pivot and the cut) and one launch of a
+//                                thread per row (the column and the next diagonals, lazily against the panel); per panel one
+//                                subtracting TN product.  No read-back: a stop flag in the workspace empties the later launches.
 // TN product: a wave owns a 32 x 32 tile of C as 2 x 2 MFMA tiles, a workgroup of four waves 64 x 64.  Lane l holds A[k0 + (l >> 4)][i0 + (l & 15)]
 // and B[k0 + (l >> 4)][j0 + (l & 15)] — the f32 16x16x4 operand maps, one double per lane — and the results
 // C[i0 + (l >> 4) + 4 r][j0 + (l & 15)], r = 0..3: the f64 C/D map, which is NOT the f32 one.  The operands are read straight
@@ -87,7 +91,8 @@ __global__ __launch_bounds__(NT) void colsum_kernel(const T* __restrict__ x, int
   sum[j] += s;
 }
 
-template <typename T, bool SHIFT, bool ACC>
+// ACC: 0 C = A^T B, 1 C += A^T B, -1 C -= A^T B (the product is summed from +0.0 first in all three)
+template <typename T, bool SHIFT, int ACC>
 __global__ __launch_bounds__(256) void tn_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
                                                  const float* __restrict__ shift, int m, int n, int k, double* __restrict__ C,
                                                  int64_t ldc) {
@@ -133,12 +138,12 @@ __global__ __launch_bounds__(256) void tn_kernel(const T* __restrict__ A, int64_
         const int row = i0 + 16 * u + lk + 4 * r, col = j0 + 16 * v + li;
         if (row < m && col < n) {
           double* c = C + (int64_t)row * ldc + col;
-          *c = ACC ? *c + acc[u][v][r] : acc[u][v][r];
+          *c = ACC > 0 ? *c + acc[u][v][r] : ACC < 0 ? *c - acc[u][v][r] : acc[u][v][r];
         }
       }
 }
 
-template <typename T, bool SHIFT, bool ACC>
+template <typename T, bool SHIFT, int ACC>
 int launch_tn(const T* A, int64_t lda, const T* B, int64_t ldb, const float* shift, int m, int n, int k, double* C, int64_t ldc,
               hipStream_t st) {
   hipLaunchKernelGGL((tn_kernel<T, SHIFT, ACC>), dim3((n + 63) / 64, (m + 63) / 64), dim3(256), 0, st, A, lda, B, ldb, shift, m, n,
@@ -297,7 +302,154 @@ __global__ __launch_bounds__(NT) void rank_kernel(const double* __restrict__ ws,
   }
 }
 
+// ---- pivoted Cholesky ------------------------------------------------------------------------------------------------------
+
+// workspace, doubles: [0] the cut, [1] the pivot of the current step, [2] its square root, [3] 1.0 once the factorisation has
+// stopped, [4 .. 8) unused; then work[d][d], the copy under factorisation; panel[nb][d], the current panel's columns, one per
+// row (the TN product's operand layout); base[d], the diagonal of work at the panel's start; diag[d], the remaining diagonal;
+// then int32: piv[d], the pivot of every step, and done[d].
+constexpr int CH_HEAD = 8;
+constexpr int CH_ROWS = 64;      // rows per workgroup of the column step: one wave
+
+struct chol_ws {
+  double *head, *work, *panel, *base, *diag;
+  int32_t *piv, *done;
+};
+
+size_t chol_bytes(int d, int nb) {
+  return ((size_t)CH_HEAD + (size_t)d * d + (size_t)nb * d + 2 * (size_t)d) * sizeof(double) + 2 * (size_t)(d + (d & 1)) * sizeof(int32_t);
+}
+
+chol_ws chol_carve(void* workspace, int d, int nb) {
+  chol_ws w;
+  w.head = (double*)workspace;
+  w.work = w.head + CH_HEAD;
+  w.panel = w.work + (size_t)d * d;
+  w.base = w.panel + (size_t)nb * d;
+  w.diag = w.base + d;
+  w.piv = (int32_t*)(w.diag + d);
+  w.done = w.piv + (d + (d & 1));
+  return w;
+}
+
+// work = a (dense), f[d][d] = 0
+__global__ __launch_bounds__(NT) void chol_begin_kernel(const double* __restrict__ a, int64_t ld, int d, double* __restrict__ work,
+                                                        double* __restrict__ f, int64_t ldf) {
+  const int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (idx >= (int64_t)d * d) return;
+  const int i = (int)(idx / d), j = (int)(idx - (int64_t)i * d);
+  work[idx] = a[(int64_t)i * ld + j];
+  f[(int64_t)i * ldf + j] = 0.0;
+}
+
+// one workgroup: the pivot of step j and the cut.  first: step j opens a panel, the remaining diagonal is that of work.
+__global__ __launch_bounds__(NT) void chol_pivot_kernel(chol_ws w, int d, int j, int first, int32_t* __restrict__ rank) {
+  __shared__ double red[NT];
+  __shared__ int redi[NT];
+  const int tid = threadIdx.x;
+  if (j > 0 && w.head[3] != 0.0) return;           // the whole workgroup: stopped at an earlier step
+  double mx = 0.0, bv = 0.0;
+  int bi = -1;
+  for (int i = tid; i < d; i += NT) {
+    double v;
+    if (first) {
+      v = w.work[(int64_t)i * d + i];
+      w.base[i] = v;
+    } else {
+      v = w.diag[i];
+    }
+    bool open = true;
+    if (j == 0) {
+      w.done[i] = 0;
+      mx = fmax(mx, v);                            // a NaN diagonal is passed over
+    } else {
+      open = w.done[i] == 0;
+    }
+    if (open && fr::chol_better(v, i, bv, bi)) {
+      bv = v;
+      bi = i;
+    }
+  }
+  if (j == 0) mx = block_max(mx, red);
+  __syncthreads();
+  red[tid] = bv;
+  redi[tid] = bi;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (tid < s && redi[tid + s] >= 0 && fr::chol_better(red[tid + s], redi[tid + s], red[tid], redi[tid])) {
+      red[tid] = red[tid + s];
+      redi[tid] = redi[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  bv = red[0];
+  bi = redi[0];
+  if (j == 0) w.head[0] = fr::chol_threshold(d, mx);
+  if (!fr::chol_go(bv, bi, w.head[0])) {
+    w.head[3] = 1.0;
+    if (j == 0) *rank = 0;
+    return;
+  }
+  w.piv[j] = bi;
+  w.done[bi] = 1;
+  w.head[1] = bv;
+  w.head[2] = sqrt(bv);
+  w.head[3] = 0.0;
+  *rank = j + 1;
+}
+
+// one thread per row: column j of the factor (step j of the panel that began at step j0) and the row's next diagonal
+template <int NB>
+__global__ __launch_bounds__(CH_ROWS) void chol_column_kernel(chol_ws w, int d, int j, int j0, double* __restrict__ f, int64_t ldf) {
+  if (w.head[3] != 0.0) return;
+  const int i = blockIdx.x * CH_ROWS + threadIdx.x;
+  if (i >= d) return;
+  const int p = w.piv[j], cnt = j - j0;
+  const double ljj = w.head[2];
+  double* mine = w.panel + i;                       // element k of this row: mine[k * d]
+  const double* pivot = w.panel + p;
+  if (w.done[i]) {                                  // rows of earlier pivots are zero in this column; the pivot's own holds L_jj
+    mine[(int64_t)cnt * d] = i == p ? ljj : 0.0;
+    if (i == p) f[(int64_t)i * ldf + j] = ljj;
+    return;
+  }
+  const double dot = fr::panel_sum<NB>(cnt, [&](int k) { return mine[(int64_t)k * d] * pivot[(int64_t)k * d]; });
+  const double c = fr::chol_entry(w.work[(int64_t)p * d + i], dot, ljj);
+  const double squares = fr::panel_sum<NB>(cnt + 1, [&](int k) {
+    const double x = k < cnt ? mine[(int64_t)k * d] : c;
+    return x * x;
+  });
+  mine[(int64_t)cnt * d] = c;
+  f[(int64_t)i * ldf + j] = c;
+  w.diag[i] = fr::chol_diag(w.base[i], squares);
+}
+
+template <int NB>
+int chol_run(const rcdm_cholesky_desc* d, chol_ws w, double* f, int32_t* rank, hipStream_t st) {
+  const int n = d->d;
+  int rc;
+  for (int j0 = 0; j0 < n; j0 += NB) {
+    const int j1 = j0 + NB < n ? j0 + NB : n;
+    for (int j = j0; j < j1; ++j) {
+      hipLaunchKernelGGL(chol_pivot_kernel, dim3(1), dim3(NT), 0, st, w, n, j, j == j0 ? 1 : 0, rank);
+      if ((rc = rcdm_check_launch()) != RCDM_OK) return rc;
+      hipLaunchKernelGGL(chol_column_kernel<NB>, dim3((n + CH_ROWS - 1) / CH_ROWS), dim3(CH_ROWS), 0, st, w, n, j, j0, f, d->ldf);
+      if ((rc = rcdm_check_launch()) != RCDM_OK) return rc;
+    }
+    // work -= panel^T panel over the whole matrix: rows and columns of earlier pivots are dead and cost nothing to carry
+    if (j1 < n && (rc = launch_tn<double, false, -1>(w.panel, n, w.panel, n, nullptr, n, n, NB, w.work, n, st)) != RCDM_OK) return rc;
+  }
+  return RCDM_OK;
+}
+
 bool misaligned8(const void* p) { return ((uintptr_t)p & 7) != 0; }
+
+int cholesky_check(const rcdm_cholesky_desc* d) {
+  if (d->d < 1 || d->ld < d->d || d->ldf < d->d || (d->nb != 0 && !fr::chol_nb_ok(d->nb))) return RCDM_EINVAL;
+  if (d->d > fr::MAX_DIM) return RCDM_ESHAPE;
+  return RCDM_OK;
+}
 
 int stats_check(const rcdm_fstats_desc* d) {
   if (d->n < 1 || d->d < 1 || d->ld < d->d) return RCDM_EINVAL;
@@ -332,8 +484,8 @@ int rcdm_feature_stats_update(const rcdm_fstats_desc* d, const void* x, const fl
   const int st1 = rcdm_check_launch();
   if (st1 != RCDM_OK) return st1;
   if (d->dtype == RCDM_FSTATS_F16)
-    return launch_tn<f16, true, true>((const f16*)x, d->ld, (const f16*)x, d->ld, shift, d->d, d->d, d->n, outer, d->d, st);
-  return launch_tn<float, true, true>((const float*)x, d->ld, (const float*)x, d->ld, shift, d->d, d->d, d->n, outer, d->d, st);
+    return launch_tn<f16, true, 1>((const f16*)x, d->ld, (const f16*)x, d->ld, shift, d->d, d->d, d->n, outer, d->d, st);
+  return launch_tn<float, true, 1>((const float*)x, d->ld, (const float*)x, d->ld, shift, d->d, d->d, d->n, outer, d->d, st);
 }
 
 int rcdm_gemm_tn_f64(int32_t m, int32_t n, int32_t k, const double* a, int64_t lda, const double* b, int64_t ldb, double* c,
@@ -341,7 +493,7 @@ int rcdm_gemm_tn_f64(int32_t m, int32_t n, int32_t k, const double* a, int64_t l
   if (!a || !b || !c || m < 1 || n < 1 || k < 1 || lda < m || ldb < n || ldc < n) return RCDM_EINVAL;
   if (misaligned8(a) || misaligned8(b) || misaligned8(c)) return RCDM_EINVAL;
   if (m > fr::MAX_DIM || n > fr::MAX_DIM || k > (1 << 30)) return RCDM_ESHAPE;
-  return launch_tn<double, false, false>(a, lda, b, ldb, nullptr, m, n, k, c, ldc, (hipStream_t)stream);
+  return launch_tn<double, false, 0>(a, lda, b, ldb, nullptr, m, n, k, c, ldc, (hipStream_t)stream);
 }
 
 int rcdm_feature_stats_finalize(int32_t d, int64_t n, const float* shift, const double* sum, const double* outer, double* mean,
@@ -435,6 +587,30 @@ int rcdm_frechet_factor(const rcdm_jacobi_desc* d, const double* w, double* f, i
   if ((rc = rcdm_check_launch()) != RCDM_OK) return rc;
   hipLaunchKernelGGL(rank_kernel, dim3(1), dim3(NT), 0, st, (const double*)ws, d->rows, d->dim, rank);
   return rcdm_check_launch();
+}
+
+size_t rcdm_cholesky_workspace_bytes(const rcdm_cholesky_desc* d) {
+  if (!d || cholesky_check(d) != RCDM_OK) return 0;
+  return chol_bytes(d->d, d->nb ? d->nb : fr::CHOL_NB);
+}
+
+int rcdm_cholesky_pivoted_f64(const rcdm_cholesky_desc* d, const double* a, double* f, int32_t* rank, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  if (!d || !a || !f || !rank) return RCDM_EINVAL;
+  int rc = cholesky_check(d);
+  if (rc != RCDM_OK) return rc;
+  if (misaligned8(a) || misaligned8(f) || ((uintptr_t)rank & 3) || misaligned8(workspace)) return RCDM_EINVAL;
+  if (!workspace || workspace_bytes < rcdm_cholesky_workspace_bytes(d)) return RCDM_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = d->d, nb = d->nb ? d->nb : fr::CHOL_NB;
+  const chol_ws w = chol_carve(workspace, n, nb);
+  const int64_t items = (int64_t)n * n;
+  hipLaunchKernelGGL(chol_begin_kernel, dim3((unsigned)((items + NT - 1) / NT)), dim3(NT), 0, st, a, d->ld, n, w.work, f, d->ldf);
+  if ((rc = rcdm_check_launch()) != RCDM_OK) return rc;
+  if (nb == 16) return chol_run<16>(d, w, f, rank, st);
+  if (nb == 32) return chol_run<32>(d, w, f, rank, st);
+  if (nb == 64) return chol_run<64>(d, w, f, rank, st);
+  return chol_run<128>(d, w, f, rank, st);
 }
 
 }  // extern "C"

@@ -9,6 +9,9 @@ downloads features, runs numpy.cov and takes scipy.linalg.sqrtm of a d x d produ
                     Fb^T Fa with S = F F^T.  Factors and singular values come from one-sided Jacobi on the device
                     (csrc/frechet_core.h); no square root of a matrix is taken, and a rank-deficient covariance (n < d) costs
                     no accuracy.  A statistics object keeps its factor until its next update: a reference set is factored once.
+                    factor="cholesky" (opt-in) takes both factors from a diagonally pivoted Cholesky factorisation instead
+                    (rcdm_cholesky_pivoted_f64: O(d) launches, the trailing updates on the float64 matrix pipe, no sweeps) and
+                    rotates only the rank_b x rank_a block of Fb^T Fa: any F with S = F F^T serves the formula.
 
 The distance does not care where the features come from: pytorch-fid's `mu` / `sigma` .npz files load with FeatureStats.load.
 The extractor built in here is the CLIP vision tower (StoryRunner(..., feature_stats=...)), so that figure is a CLIP-FD, not
@@ -36,7 +39,8 @@ class FrechetResult:
     sqrt_trace: float      # tr (Sa Sb)^(1/2)
     rank_a: int            # numerical ranks of the two covariances (rule 3)
     rank_b: int
-    sweeps: tuple          # Jacobi sweeps of (factor a, factor b, singular values); 0 for a factor that was cached
+    sweeps: tuple          # Jacobi sweeps of (factor a, factor b, singular values); 0 for a factor that was cached or is a Cholesky factor
+    block: tuple = None    # (vectors, length) of the buffer the singular-value run rotated; None when there was no such run
 
 
 def _device(device):
@@ -74,7 +78,8 @@ class FeatureStats:
         self.sum = self.outer = None     # (d,) and (d, d) float64, allocated with the first rows
         self._moments = None       # (mean, cov or None, trace or None) of the current sums
         self._given = False        # from_moments: the moments are the data, there are no sums yet
-        self._factor = None        # (F (d x rows), rank)
+        self._factor = None        # (F (d x rows), rank) from one-sided Jacobi
+        self._factor_chol = None   # (F (d x rows), rank) from the pivoted Cholesky factorisation: never handed out for the other
 
     # ---- accumulation ----
     def update(self, feats):
@@ -104,7 +109,7 @@ class FeatureStats:
         with torch.cuda.device(self.device):
             hip.feature_stats_update(desc, x.data_ptr(), self.shift.data_ptr(), self.sum.data_ptr(), self.outer.data_ptr())
         self.n += n
-        self._moments = self._factor = None
+        self._moments = self._factor = self._factor_chol = None
         return self
 
     def merge(self, other):
@@ -125,7 +130,7 @@ class FeatureStats:
         self.outer += oouter + cross + cross.T + other.n * torch.outer(delta, delta)
         self.sum += osum + other.n * delta
         self.n += other.n
-        self._moments = self._factor = None
+        self._moments = self._factor = self._factor_chol = None
         return self
 
     def _alloc(self):
@@ -205,8 +210,14 @@ class FeatureStats:
             return cls.from_moments(z["mu"], z["sigma"], n, device=device)
 
     # ---- the factor ----
-    def factor(self):
-        """-> (F (d, rows) float64 with cov = F F^T, numerical rank, sweeps run: 0 when F was cached)."""
+    def factor(self, method="jacobi"):
+        """-> (F (d, rows) float64 with cov = F F^T, numerical rank, sweeps run: 0 when F was cached).
+        method "jacobi": columns lambda_j^(1/2) v_j from one-sided Jacobi on cov.  "cholesky": columns of P L from the diagonally
+        pivoted Cholesky factorisation, the leading `rank` columns non-zero; no sweeps.  Each method keeps its own cache."""
+        if method not in ("jacobi", "cholesky"):
+            raise ValueError(f'`method` is "jacobi" or "cholesky", got {method!r}')
+        if method == "cholesky":
+            return self._cholesky()
         if self._factor is not None:
             return (*self._factor, 0)
         cov = self.cov()
@@ -222,15 +233,34 @@ class FeatureStats:
         self._factor = (f, int(count.item()))
         return (*self._factor, sweeps)
 
+    def _cholesky(self):
+        if self._factor_chol is None:
+            cov = self.cov()
+            d = self.d
+            rows = d + (d & 1)
+            desc = hip.CholeskyDesc(d, rows, d, 0)
+            ws = torch.empty(hip.cholesky_workspace_bytes(desc), dtype=torch.uint8, device=self.device)
+            f = torch.zeros(d, rows, dtype=torch.float64, device=self.device)      # the entry writes d columns: the pad one stays 0
+            rank = torch.zeros(1, dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                hip.cholesky_pivoted_f64(desc, cov.data_ptr(), f.data_ptr(), rank.data_ptr(), ws.data_ptr(), ws.numel())
+            self._factor_chol = (f, int(rank.item()))                              # the one readback
+        return (*self._factor_chol, 0)
 
-def frechet_distance(a, b):
-    """a, b: FeatureStats of one dimension on one device -> FrechetResult (host floats; the arithmetic ran on the device)."""
+
+def frechet_distance(a, b, factor="jacobi"):
+    """a, b: FeatureStats of one dimension on one device -> FrechetResult (host floats; the arithmetic ran on the device).
+    factor: how S = F F^T is formed, "jacobi" (the default) or "cholesky" (FeatureStats.factor)."""
+    if factor not in ("jacobi", "cholesky"):
+        raise ValueError(f'`factor` is "jacobi" or "cholesky", got {factor!r}')
     if a.d != b.d:
         raise ValueError(f"d differs: {a.d} and {b.d}")
     if a.device != b.device:
         raise ValueError(f"`a` is on {a.device}, `b` on {b.device}")
     d, dev = a.d, a.device
     rows = d + (d & 1)
+    if factor == "cholesky":
+        return _distance_cholesky(a, b)
     fa, rank_a, sweeps_a = a.factor()
     fb, rank_b, sweeps_b = (fa, rank_a, 0) if b is a else b.factor()
     m = torch.empty(rows, rows, dtype=torch.float64, device=dev)
@@ -244,4 +274,30 @@ def frechet_distance(a, b):
     sqrt_trace, _, mean_term, _ = out.tolist()
     trace_a, trace_b = float(a.trace().item()), float(b.trace().item())
     return FrechetResult(distance=((mean_term + trace_a) + trace_b) - 2.0 * sqrt_trace, mean_term=mean_term, trace_a=trace_a,
-                         trace_b=trace_b, sqrt_trace=sqrt_trace, rank_a=rank_a, rank_b=rank_b, sweeps=(sweeps_a, sweeps_b, sweeps_m))
+                         trace_b=trace_b, sqrt_trace=sqrt_trace, rank_a=rank_a, rank_b=rank_b, sweeps=(sweeps_a, sweeps_b, sweeps_m),
+                         block=(rows, rows))
+
+
+def _distance_cholesky(a, b):
+    """The non-zero columns of a Cholesky factor are its leading `rank` ones, so Fb^T Fa is the rank_b x rank_a block (rank_b rounded
+    up to even: the next column of Fb is zero) and the sweeps run over that alone, with dim = d for rules 2 and 3."""
+    d, dev = a.d, a.device
+    rows = d + (d & 1)
+    fa, rank_a, _ = a.factor("cholesky")
+    fb, rank_b = (fa, rank_a) if b is a else b.factor("cholesky")[:2]
+    rows_b = rank_b + (rank_b & 1)
+    out = torch.zeros(4, dtype=torch.float64, device=dev)
+    sweeps_m, block = 0, None
+    with torch.cuda.device(dev):
+        if rank_a and rank_b:
+            m = torch.empty(rows_b, rank_a, dtype=torch.float64, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            hip.gemm_tn_f64(rows_b, rank_a, d, fb.data_ptr(), rows, fa.data_ptr(), rows, m.data_ptr(), rank_a)
+            desc, ws, sweeps_m = _jacobi(m, rows_b, rank_a, d, count)
+            hip.jacobi_norm_sum(desc, m.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel())
+            block = (desc.rows, desc.len)
+        hip.frechet_mean_term(d, a.mean().data_ptr(), b.mean().data_ptr(), out[2:].data_ptr())
+    sqrt_trace, _, mean_term, _ = out.tolist()
+    trace_a, trace_b = float(a.trace().item()), float(b.trace().item())
+    return FrechetResult(distance=((mean_term + trace_a) + trace_b) - 2.0 * sqrt_trace, mean_term=mean_term, trace_a=trace_a,
+                         trace_b=trace_b, sqrt_trace=sqrt_trace, rank_a=rank_a, rank_b=rank_b, sweeps=(0, 0, sweeps_m), block=block)

@@ -124,6 +124,10 @@ class JacobiDesc(C.Structure):
     _fields_ = [("ld", C.c_int64), ("rows", C.c_int32), ("len", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CholeskyDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("ldf", C.c_int64), ("d", C.c_int32), ("nb", C.c_int32)]
+
+
 class TokAdded(C.Structure):
     _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
 
@@ -137,6 +141,7 @@ class TokenizeDesc(C.Structure):
 TOK_MAX_CAPTION, TOK_MAX_ADDED, TOK_MAX_ROWS, TOK_MAX_ADDED_LEN, TOK_MAX_RANK, TOK_MAX_CAPTIONS = 1024, 64, 66, 32, 1 << 22, 1 << 20
 FSTATS_F32, FSTATS_F16 = 0, 1                            # FStatsDesc.dtype
 FRECHET_MAX_DIM = 4096
+CHOLESKY_NB = 16                                          # fr::CHOL_NB, the panel width CholeskyDesc.nb = 0 stands for
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
 PNG_RGB, PNG_BGR = 0, 1
@@ -237,6 +242,8 @@ SYMBOLS = {
     "rcdm_jacobi_sweep": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, _P, _SZ, _P]),
     "rcdm_jacobi_norm_sum": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, _P, _SZ, _P]),
     "rcdm_frechet_factor": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, C.c_int64, _P, _P, _SZ, _P]),
+    "rcdm_cholesky_workspace_bytes": (_SZ, [C.POINTER(CholeskyDesc)]),
+    "rcdm_cholesky_pivoted_f64": (C.c_int, [C.POINTER(CholeskyDesc), _P, _P, _P, _P, _SZ, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -653,6 +660,15 @@ def jacobi_norm_sum(desc, w, out, workspace, workspace_bytes, stream=None):
 
 def frechet_factor(desc, w, f, ldf, rank, workspace, workspace_bytes, stream=None):
     _check(load().rcdm_frechet_factor(C.byref(desc), w, f, ldf, rank, workspace, workspace_bytes, _st(stream)), "rcdm_frechet_factor")
+
+
+def cholesky_workspace_bytes(desc):
+    return int(load().rcdm_cholesky_workspace_bytes(C.byref(desc)))
+
+
+def cholesky_pivoted_f64(desc, a, f, rank, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_cholesky_pivoted_f64(C.byref(desc), a, f, rank, workspace, workspace_bytes, _st(stream)),
+           "rcdm_cholesky_pivoted_f64")
 
 
 def frame_metrics_workspace_bytes(desc):
