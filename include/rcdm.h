@@ -1014,6 +1014,54 @@ int rcdm_cholesky_pivoted_f64(const rcdm_cholesky_desc* d, const double* a, doub
                               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Kernel distance: the unbiased squared maximum mean discrepancy under a polynomial kernel, over subsets of stored feature
+ * rows (KID: Binkowski et al., "Demystifying MMD GANs", 2018; here on CLIP image embeddings, a "CLIP-KID").  The companion of
+ * the Fréchet distance for few samples: no covariance, no factorisation, no sweeps.  csrc/kid_core.h holds the arithmetic,
+ * shared with tools/kid_host.cpp; restated from the definition, not pinned against torch-fidelity, torchmetrics or clean-fid.
+ *   kernel      k(x, y) = (gamma <x, y> + coef0)^degree, degree an integer in 1 .. 8 (KID: gamma = 1 / d, coef0 = 1, degree = 3).
+ *   one subset  index lists ia[0..m) into the rows of x and ib[0..m) into the rows of y, m >= 2:
+ *                 Sxx = sum over POSITIONS i != j of k(x_ia[i], x_ia[j]), Syy the same over y,
+ *                 Sxy = sum over all i, j of k(x_ia[i], y_ib[j]),
+ *                 mmd2 = (Sxx / (m (m - 1)) + Syy / (m (m - 1))) - 2 (Sxy / (m m)), evaluated in that order in float64, with
+ *                 m (m - 1) and m m formed in int64 and converted once.
+ *               The diagonal mask goes by position, not by row number: a list with a repeated row is well defined.
+ *   KID         the mean of mmd2 over the subsets and their population standard deviation (ddof = 0): the caller's to take.
+ *   arithmetic  float32 / float16 features are widened exactly (every product is exact in float64), the dot is summed in
+ *               float64 on the matrix pipe, t = fl(fl(gamma dot) + coef0) without contraction, k = ((t t) t) ... left to right.
+ *               Positions outside the subset and the masked diagonal are skipped in the epilogue (a padded row that enters
+ *               the matrix pipe as 0.0 has k = coef0^degree: zero operands mask nothing).  Every reduction has a fixed order
+ *               and no atomics — a lane's 16 values in register order, a tree over the 256 threads of a 64 x 64 tile, then the
+ *               tile partials of one (subset, block) through the fixed sum of the Fréchet entries in a second launch, which
+ *               also forms mmd2 — so the same input gives the same bits.  The symmetric blocks are computed from their
+ *               upper-triangle tiles only; an off-diagonal tile counts twice (exact).
+ *   rcdm_poly_mmd         x[nx][ldx], y[ny][ldy]: RCDM_FSTATS_F32 or _F16 rows (columns d..ld are never read); ix, iy:
+ *                         int32 [subsets][m], or null for rows 0 .. m - 1 in every subset; out: double [subsets][4] = Sxx, Syy,
+ *                         Sxy, mmd2.  All subsets and all three blocks in one launch of the tile kernel plus one of the reduce.
+ *                         Row addresses are formed in int64.  The indices are the caller's responsibility: they are not
+ *                         checked on the device.  x == y is allowed.
+ *   rcdm_poly_gram_f64    the first subset of the descriptor only: out[m][ldo >= m] = k(x_ia[i], y_ib[j]), unmasked, from the
+ *                         same tile body with a storing epilogue (a kernel matrix for other two-sample tests).
+ *   rcdm_poly_mmd_workspace_bytes   subsets x 3 x ceil(m / 64)^2 doubles (0 for a refused descriptor).
+ * RCDM_EINVAL: null descriptor, x, y or out; d < 1, m < 2, subsets, nx or ny < 1, ld < d, ldo < m, degree outside 1 .. 8, an
+ * unknown dtype, flags != 0, a misaligned pointer, a null list with m above the rows there are.  RCDM_ESHAPE: d > 4096,
+ * m > 65536, subsets > 65535.  RCDM_EWORKSPACE: workspace null or short.  All checked before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t ldx, ldy;                /* elements between rows of x and of y, >= d */
+  int32_t nx, ny, d;               /* rows of x and of y, features per row */
+  int32_t subsets, m;              /* index lists, rows per list */
+  int32_t degree;                  /* 1 .. 8 */
+  int32_t dtype;                   /* RCDM_FSTATS_* */
+  double gamma, coef0;
+  uint32_t flags;                  /* 0 */
+} rcdm_mmd_desc;
+size_t rcdm_poly_mmd_workspace_bytes(const rcdm_mmd_desc* d);
+int rcdm_poly_mmd(const rcdm_mmd_desc* d, const void* x, const void* y, const int32_t* ix, const int32_t* iy, double* out,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int rcdm_poly_gram_f64(const rcdm_mmd_desc* d, const void* x, const void* y, const int32_t* ix, const int32_t* iy, double* out,
+                       int64_t ldo, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
  * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
  * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the

@@ -128,6 +128,12 @@ class CholeskyDesc(C.Structure):
     _fields_ = [("ld", C.c_int64), ("ldf", C.c_int64), ("d", C.c_int32), ("nb", C.c_int32)]
 
 
+class MmdDesc(C.Structure):
+    _fields_ = [("ldx", C.c_int64), ("ldy", C.c_int64), ("nx", C.c_int32), ("ny", C.c_int32), ("d", C.c_int32),
+                ("subsets", C.c_int32), ("m", C.c_int32), ("degree", C.c_int32), ("dtype", C.c_int32),
+                ("gamma", C.c_double), ("coef0", C.c_double), ("flags", C.c_uint32)]
+
+
 class TokAdded(C.Structure):
     _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
 
@@ -141,6 +147,7 @@ class TokenizeDesc(C.Structure):
 TOK_MAX_CAPTION, TOK_MAX_ADDED, TOK_MAX_ROWS, TOK_MAX_ADDED_LEN, TOK_MAX_RANK, TOK_MAX_CAPTIONS = 1024, 64, 66, 32, 1 << 22, 1 << 20
 FSTATS_F32, FSTATS_F16 = 0, 1                            # FStatsDesc.dtype
 FRECHET_MAX_DIM = 4096
+KID_MAX_M, KID_MAX_SUBSETS, KID_MAX_DEGREE = 65536, 65535, 8   # kid::MAX_M, MAX_SUBSETS, MAX_DEGREE (d: FRECHET_MAX_DIM)
 CHOLESKY_NB = 16                                          # fr::CHOL_NB, the panel width CholeskyDesc.nb = 0 stands for
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
@@ -244,6 +251,9 @@ SYMBOLS = {
     "rcdm_frechet_factor": (C.c_int, [C.POINTER(JacobiDesc), _P, _P, C.c_int64, _P, _P, _SZ, _P]),
     "rcdm_cholesky_workspace_bytes": (_SZ, [C.POINTER(CholeskyDesc)]),
     "rcdm_cholesky_pivoted_f64": (C.c_int, [C.POINTER(CholeskyDesc), _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_poly_mmd_workspace_bytes": (_SZ, [C.POINTER(MmdDesc)]),
+    "rcdm_poly_mmd": (C.c_int, [C.POINTER(MmdDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_poly_gram_f64": (C.c_int, [C.POINTER(MmdDesc), _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -669,6 +679,18 @@ def cholesky_workspace_bytes(desc):
 def cholesky_pivoted_f64(desc, a, f, rank, workspace, workspace_bytes, stream=None):
     _check(load().rcdm_cholesky_pivoted_f64(C.byref(desc), a, f, rank, workspace, workspace_bytes, _st(stream)),
            "rcdm_cholesky_pivoted_f64")
+
+
+def poly_mmd_workspace_bytes(desc):
+    return int(load().rcdm_poly_mmd_workspace_bytes(C.byref(desc)))
+
+
+def poly_mmd(desc, x, y, ix, iy, out, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_poly_mmd(C.byref(desc), x, y, ix, iy, out, workspace, workspace_bytes, _st(stream)), "rcdm_poly_mmd")
+
+
+def poly_gram_f64(desc, x, y, ix, iy, out, ldo, stream=None):
+    _check(load().rcdm_poly_gram_f64(C.byref(desc), x, y, ix, iy, out, ldo, _st(stream)), "rcdm_poly_gram_f64")
 
 
 def frame_metrics_workspace_bytes(desc):

@@ -206,7 +206,7 @@ class StoryRunner:
     def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
                  save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=(),
-                 stage2_autoreg=False, frames_dir=None, grid_dir=None, feature_stats=None):
+                 stage2_autoreg=False, frames_dir=None, grid_dir=None, feature_stats=None, feature_banks=None):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
@@ -219,6 +219,9 @@ class StoryRunner:
         the 5 S generated frames are added to `generated` (the forward "clip_i" runs, done once when both are asked for) and
         target_embeds to `reference`, for a set-level Fréchet distance (frechet_distance; a CLIP-FD) over as many calls as the
         caller likes.  Its requirements are those of "clip_i".  None: nothing more is launched.
+        feature_banks: (generated, reference), two rcdms_amd.kid.FeatureBank of the embedding width: the same rows, kept rather
+        than summed, for a kernel distance (kernel_distance; a CLIP-KID).  The same forward, the same requirements.  None: nothing
+        more is launched.
         stage2_autoreg: the stage-2 driver's --autoreg loop (stage2…:304-362) for the S stories, independent of `autoreg`
         (stage 1's loop): five stage-2 calls at batch S, pass i keeping frame i of every story —
           pass 0: the call of stage2_autoreg=False (given frame 0 seen, image_embeds_1 its hidden state, proj_embeds_0
@@ -249,13 +252,15 @@ class StoryRunner:
                              "there and fails at stage2_batchtest_rcdms_model.py:367 — run mode=\"continue\", or stage2=False")
         if stage2 and self.stage2_pipe is None:
             raise ValueError("stage 2 asked for, but the runner was built without a stage-2 pipeline")
-        if feature_stats is not None:
-            if len(feature_stats) != 2:
-                raise ValueError("feature_stats is a pair (generated, reference) of FeatureStats")
+        for name, pair, kind in (("feature_stats", feature_stats, "FeatureStats"), ("feature_banks", feature_banks, "FeatureBank")):
+            if pair is None:
+                continue
+            if len(pair) != 2:
+                raise ValueError(f"{name} is a pair (generated, reference) of {kind}")
             if not stage2:
-                raise ValueError("feature_stats collect the embeddings of the frames stage 2 generates: this call runs no stage 2")
+                raise ValueError(f"{name} collect the embeddings of the frames stage 2 generates: this call runs no stage 2")
             if output_type != "uint8" and not stage2_autoreg:
-                raise ValueError(f"feature_stats are taken from uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
+                raise ValueError(f"{name} are taken from uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
         if metrics and not stage2:
             raise ValueError(f"metrics {metrics} compare the frames stage 2 generates with their targets: this call runs no stage 2")
         if stage2_autoreg and not stage2:
@@ -337,8 +342,9 @@ class StoryRunner:
                 write_story_pngs(frames_dir, grid_dir, indices, frames_u8,
                                  self.target_frames(frames) if grid_dir is not None else None, files)
         figures = {}
-        if metrics or feature_stats is not None:
-            figures = self.story_metrics(frames_u8 if stage2_autoreg else videos, frames, target, metrics, feature_stats)
+        if metrics or feature_stats is not None or feature_banks is not None:
+            figures = self.story_metrics(frames_u8 if stage2_autoreg else videos, frames, target, metrics, feature_stats,
+                                         feature_banks)
         return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures,
                            frames_u8=frames_u8 if stage2_autoreg else None)
 
@@ -384,10 +390,10 @@ class StoryRunner:
         r = resampler(flat.shape[1], flat.shape[2], ft.height, ft.width, ft.resample, None, flat.device)
         return r.to_uint8(flat, ft.flip_channels).view(S, FRAMES, ft.height, ft.width, 3)
 
-    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None):
+    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None, feature_banks=None):
         """videos: uint8 (S, 5, H, W, 3) as stage 2 returns them; frames: the given uint8 (S, 5, Hs, Ws, 3) on the device.
         -> {name: (S, 5) tensor} for the names in `metrics`.  feature_stats: (generated, reference) FeatureStats that take the
-        embeddings of `videos` and target_embeds."""
+        embeddings of `videos` and target_embeds; feature_banks: (generated, reference) FeatureBanks that keep the same rows."""
         from .metrics import frame_metrics
         S = videos.shape[0]
         out = {}
@@ -397,12 +403,16 @@ class StoryRunner:
                 out["ssim"] = fm.ssim.view(S, FRAMES)
             if "psnr" in metrics:
                 out["psnr"] = fm.psnr.view(S, FRAMES)
-        if "clip_i" in metrics or feature_stats is not None:
+        if "clip_i" in metrics or feature_stats is not None or feature_banks is not None:
             e = self.image_encoder(self._pixels(videos.reshape(S * FRAMES, *videos.shape[2:]))).image_embeds
         if feature_stats is not None:
             generated, reference = feature_stats
             generated.update(e.reshape(S * FRAMES, -1))
             reference.update(target_embeds.reshape(S * FRAMES, -1))
+        if feature_banks is not None:
+            generated, reference = feature_banks
+            generated.append(e.reshape(S * FRAMES, -1))
+            reference.append(target_embeds.reshape(S * FRAMES, -1))
         if "clip_i" in metrics:
             out["clip_i"] = torch.nn.functional.cosine_similarity(e.reshape(S, FRAMES, -1).float(), target_embeds.float(), dim=-1)
         return out
