@@ -29,6 +29,7 @@
 #include <string.h>
 #include "common.h"
 #include "igemm_plan.h"
+#include "igemm_loader.h"
 #include "gn_plan.h"
 #ifndef RCDM_LNX_ABLATE
 #define RCDM_LNX_ABLATE 0   // debug builds (tools/lnx_bench.py): 1 = no partial-statistics loads, 64 = no accumulator transform, 128 = no table write, 256 = no producer statistics
@@ -176,97 +177,42 @@ void igemm_dma_kernel(const IgemmArgs p) {
   const int nkl = ks_end - ks_begin;
   if (my_tiles == 0 || nkl <= 0) return;
 
-  // XCD-aware, L2-blocked tile order.  Block b runs on XCD b%8, so each XCD is given a contiguous run of the tile
-  // sequence; the sequence itself walks super-rows of GM row panels column by column (n outer, m inner inside the
-  // super-row), so the ~64 tiles an XCD has in flight form a GM x (64/GM) patch: every activation panel is shared
-  // by 64/GM tiles and every weight panel by GM tiles *at the same time*.  With plain n-fastest order a wide N
-  // (GEGLU: 40-80 column tiles) streams the whole weight matrix through the 4 MB L2 once per row panel: rocprofv3
-  // FETCH_SIZE showed 16-19x the operand bytes (0.4-0.5 GB per launch, HBM-bound) on the 32x32 / 16x16 levels.
-  constexpr int GM = 8;
   auto tile_of = [&](int i, int& m0, int& n0) __attribute__((always_inline)) {
-    const int lin = (int)blockIdx.x + i * G;
-    const int xcd = lin & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int tl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    const int per_group = GM * p.tilesN;
-    const int grp = tl / per_group, rem = tl - grp * per_group;
-    const int gm = min(GM, p.tilesM - grp * GM);  // rows in this (possibly last, short) super-row
-    const int tn = rem / gm, tm = grp * GM + (rem - tn * gm);
-    m0 = tm * BM_;
-    n0 = tn * BN_;
+    igemm_tile_origin<BM_, BN_>(p, (int)blockIdx.x + i * G, m0, n0);
   };
 
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc((void*)(TAPS == 9 ? p.A2 : p.A), 0, 0x7FFFFFFF, 0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
   const int Hv = p.Hi << p.up, Wv = p.Wi << p.up;
 
   // ---- loader state of the tile currently being ISSUED (static-indexed arrays: fully unrolled) ----------------
   const int lrow = lane >> 3, lch = lane & 7;
-  unsigned a_off[AI], w_off[BI];
-  int a_img[AI], a_iy[AI], a_ix[AI], a_c[AI], w_c[BI];
+  IgemmPixelRow a_row[AI];
+  unsigned w_off[BI];
+  int a_c[AI], w_c[BI];
   auto setup_loader = [&](int m0, int n0) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
       const int row = (wave * AI + i) * 8 + lrow;
-      const int m = m0 + row;
-      a_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-      a_off[i] = OOB;
-      a_img[i] = a_iy[i] = a_ix[i] = 0;
-      if (TAPS == 1) {
-        if (m < p.M) a_off[i] = (unsigned)m * (unsigned)p.lda * 2u;
-      } else {
-        const int hw = p.Ho * p.Wo;
-        const int img = m / hw, rem = m - img * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        a_img[i] = img;
-        a_iy[i] = m < p.M ? oy * p.stride - p.pad : -(1 << 20);
-        a_ix[i] = ox * p.stride - p.pad;
-      }
+      a_c[i] = igemm_swizzle_chunk(row, lch);
+      a_row[i] = igemm_pixel_row<TAPS>(p, m0 + row, m0 + row < p.M);
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
       const int row = (wave * BI + i) * 8 + lrow;
-      const int n = n0 + row;
-      w_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-      w_off[i] = n < p.N ? (unsigned)n * (unsigned)p.Ktot * 2u : OOB;
+      w_c[i] = igemm_swizzle_chunk(row, lch);
+      w_off[i] = igemm_weight_row(p, n0 + row);
     }
   };
 
   auto issue = [&](int ks, int stage) __attribute__((always_inline)) {
-    int tap = 0, kci = ks;
-    if (TAPS != 1) {
-      // channel chunk outer, tap inner: the nine shifted windows of one 64-channel slab are read back to back, so
-      // the re-reads hit L2 (one slab of all tiles in flight on an XCD is ~2 MB).  Tap-outer order re-read the whole
-      // Cin-deep panel (16 MB in flight at Cin = 960) per tap: FETCH_SIZE was 10x the input bytes.
-      kci = ks / 9;
-      tap = ks - kci * 9;
-    }
-    // second input (IgemmArgs::A2, conv launches only): the k-steps from nk1 on are a tenth "tap" — the output pixel itself
-    // in another tensor with its own row stride and channel count, against W columns 9 Cin + c
-    const bool s2 = TAPS == 9 && ks >= p.nk1;   // (wave-uniform)
-    if (s2) {
-      kci = ks - p.nk1;
-      tap = 9;
-    }
-    const int c0 = kci * BK;
-    const int dy = s2 ? 1 : tap / 3, dx = s2 ? 1 : tap - dy * 3;
-    const int cin = s2 ? p.Cin2 : p.Cin;
-    const unsigned lda = (unsigned)(s2 ? p.lda2 : p.lda);
+    const IgemmKStep k = igemm_kstep<TAPS>(p, ks);
     char* sbase = smem + stage * STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-      const int c = c0 + a_c[i];
-      unsigned vo;
-      if (TAPS == 1) {
-        vo = (c < p.Cin && a_off[i] != OOB) ? a_off[i] + (unsigned)c * 2u : OOB;
-      } else {
-        const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
-        const bool ok = (c < cin) && ((unsigned)iy < (unsigned)Hv) && ((unsigned)ix < (unsigned)Wv);
-        const int sy = iy >> p.up, sx = ix >> p.up;
-        vo = ok ? ((unsigned)((a_img[i] * p.Hi + sy) * p.Wi + sx) * lda + (unsigned)c) * 2u : OOB;
-      }
-      if (TAPS == 9 && s2)
+      const unsigned vo = igemm_pixel_offset<TAPS>(p, k, a_row[i], k.c0 + a_c[i], Hv, Wv);
+      if (TAPS == 9 && k.s2)   // (wave-uniform)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rsrcA2, (__attribute__((address_space(3))) void*)(sbase + (wave * AI + i) * 1024), 16, vo, 0, 0, 0);
       else
@@ -275,9 +221,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
-      const int c = c0 + w_c[i];
-      const unsigned vo = (c < cin && w_off[i] != OOB)
-                              ? w_off[i] + ((unsigned)tap * (unsigned)p.Cin + (unsigned)c) * 2u : OOB;
+      const unsigned vo = igemm_weight_offset(p, k, w_off[i], k.c0 + w_c[i]);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           rsrcW, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + (wave * BI + i) * 1024), 16, vo, 0, 0, 0);
     }

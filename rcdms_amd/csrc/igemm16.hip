@@ -16,6 +16,7 @@
 // after the barrier that opens step g.  One tile per block, XCD-aware tile order; epilogue through igemm_epilogue.h.
 #include "common.h"
 #include "igemm_plan.h"
+#include "igemm_loader.h"
 #include "pp_sync.h"
 #include "igemm_epilogue.h"
 #ifndef RCDM_I16_ABLATE
@@ -39,18 +40,7 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
   if (nkl <= 0) return;
 
   int cm0, cn0;
-  {
-    const int ntiles = p.tilesM * p.tilesN, lin = blockIdx.x;
-    const int xcd = lin & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int tl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    constexpr int GM = 8;
-    const int per_group = GM * p.tilesN;
-    const int sg = tl / per_group, rem = tl - sg * per_group;
-    const int gm = min(GM, p.tilesM - sg * GM);
-    const int tn = rem / gm, tm = sg * GM + (rem - tn * gm);
-    cm0 = tm * BM;
-    cn0 = tn * BN;
-  }
+  igemm_tile_origin<BM, BN>(p, blockIdx.x, cm0, cn0);
 
   // deferred LayerNorm of the A rows (rcdm_gemm_lnx): thread t < BM requests row t's partial statistics FIRST — the loader
   // set-up and the first operand stage cover the round trip — and carries (rstd, mean rstd) in two registers to the epilogue
@@ -62,68 +52,27 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc((void*)(TAPS == 9 ? p.A2 : p.A), 0, 0x7FFFFFFF, 0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
   const int Hv = p.Hi << p.up, Wv = p.Wi << p.up;
   const int lrow = lane >> 3, lch = lane & 7;
 
-  // ---- loader state (static-indexed arrays: fully unrolled)
-  unsigned a_off[NP], w_off[NP];
-  int a_img[NP], a_iy[NP], a_ix[NP], a_c[NP], w_c[NP];
+  // ---- loader state (static-indexed arrays: fully unrolled); a wave's pixel and weight pieces are the same tile rows
+  IgemmPixelRow a_row[NP];
+  unsigned w_off[NP];
+  int a_c[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int row = (wave * NP + i) * 8 + lrow;
-    const int m = cm0 + row;
-    a_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-    a_off[i] = OOB;
-    a_img[i] = a_ix[i] = 0;
-    a_iy[i] = -(1 << 20);
-    if (TAPS == 1) {
-      if (m < p.M) a_off[i] = (unsigned)m * (unsigned)p.lda * 2u;
-    } else if (m < p.M) {
-      const int hw = p.Ho * p.Wo;
-      const int img = m / hw, rem = m - img * hw;
-      const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-      a_img[i] = img * p.Hi * p.Wi;
-      a_iy[i] = oy * p.stride - p.pad;
-      a_ix[i] = ox * p.stride - p.pad;
-    }
-    const int n = cn0 + row;
-    w_c[i] = a_c[i];
-    w_off[i] = n < p.N ? (unsigned)n * (unsigned)p.Ktot * 2u : OOB;
+    a_c[i] = igemm_swizzle_chunk(row, lch);
+    a_row[i] = igemm_pixel_row<TAPS>(p, cm0 + row, cm0 + row < p.M);
+    w_off[i] = igemm_weight_row(p, cn0 + row);
   }
   auto issue = [&](int g, int stage) __attribute__((always_inline)) {
-    const int ks = ks_begin + g;
-    int tap = 0, kci = ks;
-    // second input (IgemmArgs::A2, conv launches only): the k-steps from nk1 on are a tenth "tap" — the output pixel itself
-    // (dy = dx = 1 from the padded origin) in ANOTHER tensor with its own row stride and channel count; W column 9 Cin + c
-    const bool s2 = TAPS == 9 && ks >= p.nk1;
-    if (TAPS != 1) {  // channel chunk outer, tap inner
-      kci = ks / 9;
-      tap = ks - kci * 9;
-      if (s2) {
-        kci = ks - p.nk1;
-        tap = 9;
-      }
-    }
-    const int c0 = kci * BK;
-    const int dy = s2 ? 1 : tap / 3, dx = s2 ? 1 : tap - dy * 3;
-    const int cin = s2 ? p.Cin2 : p.Cin;
-    const unsigned lda = (unsigned)(s2 ? p.lda2 : p.lda);
+    const IgemmKStep k = igemm_kstep<TAPS>(p, ks_begin + g);
     char* sbase = smem + stage * STAGE;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const int c = c0 + a_c[i];
-      unsigned vo;
-      if (TAPS == 1) {
-        vo = (c < p.Cin && a_off[i] != OOB) ? a_off[i] + (unsigned)c * 2u : OOB;
-      } else {
-        const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
-        const bool ok = (c < cin) && ((unsigned)iy < (unsigned)Hv) && ((unsigned)ix < (unsigned)Wv);
-        const int sy = iy >> p.up, sx = ix >> p.up;
-        const unsigned off = ((unsigned)(a_img[i] + sy * p.Wi + sx) * lda + (unsigned)c) * 2u;
-        vo = ok ? off : OOB;
-      }
-      if (TAPS == 9 && s2)   // (wave-uniform: ks is)
+      const unsigned vo = igemm_pixel_offset<TAPS>(p, k, a_row[i], k.c0 + a_c[i], Hv, Wv);
+      if (TAPS == 9 && k.s2)   // (wave-uniform: ks is)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rsrcA2, (__attribute__((address_space(3))) void*)(sbase + (wave * NP + i) * 1024), 16, vo, 0, 0, 0);
       else
@@ -135,9 +84,7 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
 #endif
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const int c = c0 + w_c[i];
-      const unsigned vo = (c < cin && w_off[i] != OOB)
-                              ? w_off[i] + ((unsigned)tap * (unsigned)p.Cin + (unsigned)c) * 2u : OOB;
+      const unsigned vo = igemm_weight_offset(p, k, w_off[i], k.c0 + a_c[i]);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           rsrcW, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + (wave * NP + i) * 1024), 16, vo, 0, 0, 0);
     }

@@ -34,6 +34,7 @@
 // vmcnt immediates wave-dependent: picked by a wave-uniform branch.
 #include "common.h"
 #include "igemm_plan.h"
+#include "igemm_loader.h"
 #include "pp_sync.h"
 #include "igemm_epilogue.h"
 
@@ -68,65 +69,37 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
   const int nkl = min(p.nk, ks_begin + p.nk_per_split) - ks_begin;
   if (nkl <= 0) return;
 
-  // XCD-aware, L2-blocked tile order (see igemm.hip): block b runs on XCD b % 8 and each XCD gets a contiguous run of
-  // the sequence "super-rows of 8 row panels, column by column".
   int cm0, cn0;
-  {
-    const int ntiles = p.tilesM * p.tilesN, lin = blockIdx.x;
-    const int xcd = lin & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int tl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-    constexpr int GM = 8;
-    const int per_group = GM * p.tilesN;
-    const int sg = tl / per_group, rem = tl - sg * per_group;
-    const int gm = min(GM, p.tilesM - sg * GM);
-    const int tn = rem / gm, tm = sg * GM + (rem - tn * gm);
-    cm0 = tm * BM;
-    cn0 = tn * BN;
-  }
+  igemm_tile_origin<BM, BN>(p, blockIdx.x, cm0, cn0);
 
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc((void*)(TAPS == 9 ? p.A2 : p.A), 0, 0x7FFFFFFF, 0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
   const int Hv = p.Hi << p.up, Wv = p.Wi << p.up;
 
   const int phase = TAPS == 4 ? cm0 / p.ph_rows : 0;   // phase launch (IgemmArgs::ph_rows): the tile's output parity (2a + b)
   // ---- loader state: every group fills the OTHER group's pixel rows; group 0 the lower weight rows, group 1 the upper
   const int myhalf = grp ^ 1, mywhalf = grp;
   const int lrow = lane >> 3, lch = lane & 7;
-  unsigned a_off[NPP], w_off[NPW];
-  int a_img[NPP], a_iy[NPP], a_ix[NPP], a_c[NPP], a_lds[NPP], w_c[NPW], w_lds[NPW];
+  IgemmPixelRow a_row[NPP];
+  unsigned w_off[NPW];
+  int a_c[NPP], a_lds[NPP], w_c[NPW], w_lds[NPW];
 #pragma unroll
   for (int i = 0; i < NPP; ++i) {
     const int q = wn + 4 * i;
     const bool live = q < PP;
     const int row = myhalf * HM + q * 8 + lrow;  // row of the pixel tile
-    const int m = cm0 + row;
     a_lds[i] = live ? (myhalf * HM + q * 8) * 128 : -1;
-    a_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-    a_off[i] = OOB;
-    a_img[i] = a_ix[i] = 0;
-    a_iy[i] = -(1 << 20);
-    if (TAPS == 1) {
-      if (live && m < p.M) a_off[i] = (unsigned)m * (unsigned)p.lda * 2u;
-    } else if (live && m < p.M) {
-      const int hw = p.Ho * p.Wo;
-      const int pm = TAPS == 4 ? m - phase * p.ph_rows : m;   // (phase launch: the source pixel of this virtual row)
-      const int img = pm / hw, rem = pm - img * hw;
-      const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-      a_img[i] = img * p.Hi * p.Wi;  // first pixel row of the image
-      a_iy[i] = oy * p.stride - p.pad + (TAPS == 4 ? phase >> 1 : 0);
-      a_ix[i] = ox * p.stride - p.pad + (TAPS == 4 ? phase & 1 : 0);
-    }
+    a_c[i] = igemm_swizzle_chunk(row, lch);
+    a_row[i] = igemm_pixel_row<TAPS>(p, cm0 + row, live && cm0 + row < p.M, phase);
   }
 #pragma unroll
   for (int i = 0; i < NPW; ++i) {
     const int q = wn + 4 * i;
     const int row = mywhalf * HN + q * 8 + lrow;  // row of the weight tile
-    const int n = cn0 + row;
     w_lds[i] = W_RING + (mywhalf * HN + q * 8) * 128;
-    w_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-    w_off[i] = n < p.N ? (unsigned)(phase * p.N + n) * (unsigned)p.Ktot * 2u : OOB;
+    w_c[i] = igemm_swizzle_chunk(row, lch);
+    w_off[i] = igemm_weight_row(p, cn0 + row, phase);
   }
 
   // Every tile of an XCD that shares a weight panel would otherwise stream the SAME weight lines at the same moment
@@ -137,49 +110,22 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
     const int idx = blockIdx.x >> 3;  // position inside the XCD's run of tiles
     rot = TAPS == 1 ? idx % nkl : (TAPS * idx) % nkl;
   }
-  auto kpos = [&](int ks, int& c0, int& tap) __attribute__((always_inline)) {
+  auto kpos = [&](int ks) __attribute__((always_inline)) {   // loop step -> what it reads
     ks += rot;
     if (ks >= nkl) ks -= nkl;
-    ks += ks_begin;
-    tap = 0;
-    int kci = ks;
-    if (TAPS != 1) {  // channel chunk outer, tap inner (the nine windows of one 64-channel slab re-hit L2)
-      kci = ks / TAPS;
-      tap = ks - kci * TAPS;
-      if (TAPS == 9 && ks >= p.nk1) {   // second input (IgemmArgs::A2): a tenth "tap" = the output pixel itself in another tensor
-        kci = ks - p.nk1;
-        tap = 9;
-      }
-    }
-    c0 = kci * BK;
+    return igemm_kstep<TAPS>(p, ks_begin + ks);
   };
   auto issue_px = [&](int ks) __attribute__((always_inline)) {
     const int slot = ks & 1;
-    int c0, tap;
-    kpos(ks, c0, tap);
-    const bool s2 = TAPS == 9 && tap == 9;   // (wave-uniform)
-    const int dy = s2 ? 1 : TAPS == 4 ? tap >> 1 : tap / 3, dx = s2 ? 1 : TAPS == 4 ? tap & 1 : tap - dy * 3;
-    const int cin = s2 ? p.Cin2 : p.Cin;
-    const unsigned lda = (unsigned)(s2 ? p.lda2 : p.lda);
+    const IgemmKStep k = kpos(ks);
 #if defined(RCDM_PP_ABLATE) && (RCDM_PP_ABLATE & 8)   // bound of a halo-staged pixel tile: the pixel pieces of 2 taps in 9 only (garbage results)
-    if (TAPS != 1 && tap >= 2) return;
+    if (TAPS != 1 && k.tap >= 2) return;
 #endif
 #pragma unroll
     for (int i = 0; i < NPP; ++i) {
-      const int c = c0 + a_c[i];
-      unsigned vo;
-      if (TAPS == 1) {
-        vo = (c < p.Cin && a_off[i] != OOB) ? a_off[i] + (unsigned)c * 2u : OOB;
-      } else {
-        const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
-        const bool ok = (c < cin) && ((unsigned)iy < (unsigned)Hv) && ((unsigned)ix < (unsigned)Wv);
-        const int sy = iy >> p.up, sx = ix >> p.up;
-        // computed unconditionally (a select, not a branch: no address is dereferenced here)
-        const unsigned off = ((unsigned)(a_img[i] + sy * p.Wi + sx) * lda + (unsigned)c) * 2u;
-        vo = ok ? off : OOB;
-      }
+      const unsigned vo = igemm_pixel_offset<TAPS>(p, k, a_row[i], k.c0 + a_c[i], Hv, Wv);
       if (a_lds[i] >= 0) {  // wave-uniform: the waves whose last piece does not exist issue one DMA fewer
-        if (TAPS == 9 && s2)
+        if (TAPS == 9 && k.s2)   // (wave-uniform)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(
               rsrcA2, (__attribute__((address_space(3))) void*)(smem + slot * A_BYTES + a_lds[i]), 16, vo, 0, 0, RCDM_PP_AAUX);
         else
@@ -190,14 +136,10 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
   };
   auto issue_w = [&](int ks) __attribute__((always_inline)) {
     const int slot = ks % 3;
-    int c0, tap;
-    kpos(ks, c0, tap);
-    const int cin = (TAPS == 9 && tap == 9) ? p.Cin2 : p.Cin;
+    const IgemmKStep k = kpos(ks);
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
-      const int c = c0 + w_c[i];
-      const unsigned vo = (c < cin && w_off[i] != OOB)
-                              ? w_off[i] + ((unsigned)tap * (unsigned)p.Cin + (unsigned)c) * 2u : OOB;
+      const unsigned vo = igemm_weight_offset(p, k, w_off[i], k.c0 + w_c[i]);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           rsrcW, (__attribute__((address_space(3))) void*)(smem + slot * W_BYTES + w_lds[i]), 16, vo, 0, 0, RCDM_PP_WAUX);
     }

@@ -1,6 +1,8 @@
-// igemm_args.h — launch arguments shared by the two implicit-GEMM kernel families of librcdm_hip.so:
-// igemm.hip (igemm_dma_kernel: 4-wave 128x128 / 64x64 / 128x64 tiles and the 8-wave 256x256 one-barrier loop) and
-// igemm8.hip (igemm_pp_kernel: 8-wave ping-pong loop, 160x320 / 160x256 / 256x256 tiles).
+// igemm_args.h — launch arguments shared by the implicit-GEMM kernels of librcdm_hip.so:
+// igemm.hip (igemm_dma_kernel: 4-wave 128x128 / 64x64 / 128x64 tiles and the 8-wave 256x256 one-barrier loop),
+// igemm8.hip (igemm_pp_kernel: 8-wave ping-pong loop, 160x320 / 160x256 / 256x256 tiles), igemm16.hip (igemm16_kernel:
+// 4-wave 160x160 tiles) and wino.hip (the position GEMM of the Winograd conv).  The operand addressing the first three derive
+// from these fields is igemm_loader.h.
 #pragma once
 #include "common.h"
 

@@ -6,7 +6,13 @@
 2. The model is mutated in one place at a time — the defects an implicit GEMM can have that move one term — and every
    mutation breaks exact equality.  Next to each, the same mutation is applied to the 2880-term convolution (320 channels,
    3x3) on the kernel suites' usual operands (randn activations, randn * K^-0.5 weights) and the share of the touched
-   elements that close() of tests/test_hip_kernels.py still accepts is printed: what the tolerance lets through."""
+   elements that close() of tests/test_hip_kernels.py still accepts is printed: what the tolerance lets through.
+3. The operand addressing the three tile kernels share (rcdms_amd/csrc/igemm_loader.h) runs on the CPU
+   (tools/igemm_loader_host.cpp): the operands gathered through its offsets are the model's A and W, the tile order is a
+   bijection, and one moved border tap breaks the comparison."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -229,3 +235,193 @@ def test_mutation_second_input_order():
     x, w, x2, w2 = _randn_conv(cin2=320)
     _share("second input's k-step swapped with the last tap", X.conv_problem(x, w, x2=x2, w2=w2, mutate="swap_second_input_with_last_tap").acc(),
            X.conv_problem(x, w, x2=x2, w2=w2).acc())
+
+
+# ---- 3. the kernels' operand addressing (csrc/igemm_loader.h), run on the CPU by tools/igemm_loader_host.cpp -----------------
+# For every case the GPU file launches, at every tile shape the planner gives it: gathering the raw input and the packed
+# weight through the offsets the kernels would hand to the DMA (out of bounds read as 0) gives the A and W matrices of the
+# case's Problem, columns in k order per k-step of 64.  Integer arrays, compared with ==.
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NO_SEG2 = 0x7fffffff
+POISON = 777.0           # the padding behind a row's channels (lda > c_in): no operand has this value
+LOADER_FIELDS = ("M", "N", "Cin", "Ktot", "Hi", "Wi", "Ho", "Wo", "stride", "up", "pad", "lda", "nk", "nk1", "Cin2", "lda2", "ph_rows",
+                 "tilesM", "tilesN")
+
+
+@pytest.fixture(scope="module")
+def loader_tool(tmp_path_factory):
+    """tools/igemm_loader_host.cpp built with the project's compiler (host side only), no sanitizer flags."""
+    from rcdms_amd import build
+    exe = str(tmp_path_factory.mktemp("igemm_loader") / "igemm_loader_host")
+    cmd = [build.HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O2", "-I", build.CSRC,
+           os.path.join(ROOT, "tools", "igemm_loader_host.cpp"), "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 0, r.stdout.decode(errors="replace")
+    return exe
+
+
+def loader_args(taps, bm, bn, geom):
+    f = dict(Hi=1, Wi=1, Ho=1, Wo=1, stride=1, up=0, pad=1, nk1=NO_SEG2, Cin2=0, lda2=0, ph_rows=0)
+    f.update(geom)
+    return [str(v) for v in [taps, bm, bn] + [f[k] for k in LOADER_FIELDS]]
+
+
+def run_loader(tool, taps, bm, bn, geom):
+    """The tool's records [n][7]: (kind, tile, k-step, tile row, lane chunk, first channel within the k-step, byte offset | -1)."""
+    r = subprocess.run([tool] + loader_args(taps, bm, bn, geom), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")
+    return np.fromstring(r.stdout.decode(), dtype=np.int64, sep=" ").reshape(-1, 7)
+
+
+def padded_rows(a, ld):
+    """[rows][c] -> the flat buffer of rows of stride ld, POISON behind the channels."""
+    out = np.full((a.shape[0], ld), POISON)
+    out[:, :a.shape[1]] = a
+    return out.reshape(-1)
+
+
+def in_k_steps(mat, steps, rows):
+    """A Problem's matrix as the kernels see it: [rows][nk * 64], k-step ks at columns ks * 64, zeros where a row, or a
+    channel of a short k-step, does not exist."""
+    out = np.zeros((rows, len(steps) * X.BK))
+    for ks, (lo, hi) in enumerate(steps):
+        out[:mat.shape[0], ks * X.BK:ks * X.BK + hi - lo] = mat[:, lo:hi]
+    return out
+
+
+def _gather(rec, raws, want, rows_of, tile_rows, nk):
+    """rec: the records of one operand.  True if the values behind the offsets equal want[row][k-step columns]."""
+    kind, lin, ks, row, lch, c, off = rec.T
+    assert ((c % 8 == 0) & (c >= 0) & (c < X.BK) & (lch >= 0) & (lch < 8) & (row >= 0) & (row < tile_rows)).all()
+    n_tiles = int(lin.max()) + 1
+    assert len(rec) == n_tiles * nk * tile_rows * 8, "a piece is missing or printed twice"
+    for chunk in (c // 8, lch):        # every (tile, k-step, row) has each source chunk and each LDS slot once: the swizzle is a bijection
+        assert np.unique(((lin * nk + ks) * tile_rows + row) * 8 + chunk).size == len(rec)
+    vals = np.zeros((len(rec), 8))
+    for k, raw in raws.items():
+        sel = (kind == k) & (off >= 0)
+        assert (off[sel] % 16 == 0).all(), "a DMA piece that is not 16-byte aligned"
+        first = off[sel] // 2
+        assert (first + 8 <= raw.size).all(), "an offset past the end of the operand"
+        vals[sel] = raw[first[:, None] + np.arange(8)]
+    assert np.isin(kind[off >= 0], list(raws)).all()
+    return bool((vals == want[rows_of(lin, row)[:, None], (ks * X.BK + c)[:, None] + np.arange(8)]).all())
+
+
+def gathered_equals_model(rec, bm, bn, plan, raw_a, raw_w, A_want, W_want, nk1=NO_SEG2, raw_a2=None, ph_rows=0):
+    """rec: the tool's output for one (case, tile shape).  A_want [tilesM * bm][nk * 64], W_want [phase][tilesN * bn][nk * 64]."""
+    tm, tn, nk = plan["tiles_m"], plan["tiles_n"], plan["k_steps"]
+    tiles = rec[rec[:, 0] == 3]
+    assert (tiles[:, 1] == np.arange(tm * tn)).all()
+    assert sorted(zip(tiles[:, 2].tolist(), tiles[:, 3].tolist())) == [(i * bm, j * bn) for i in range(tm) for j in range(tn)]
+    m0, n0 = tiles[:, 2], tiles[:, 3]
+    act, wgt = rec[rec[:, 0] <= 1], rec[rec[:, 0] == 2]
+    assert ((act[:, 0] == 1) == (act[:, 2] >= nk1)).all(), "the second input is read at the k-steps from nk1 on, and only there"
+    raws = {0: raw_a} if raw_a2 is None else {0: raw_a, 1: raw_a2}
+    ok_a = _gather(act, raws, A_want, lambda lin, row: m0[lin] + row, bm, nk)
+    phase_rows = W_want.shape[1]
+    ok_w = _gather(wgt, {2: raw_w}, W_want.reshape(-1, W_want.shape[2]),
+                   lambda lin, row: (m0[lin] // ph_rows if ph_rows else 0) * phase_rows + n0[lin] + row, bn, nk)
+    return ok_a and ok_w
+
+
+def tile_plans(hip, query, desc, variants=range(1, 11), usable=lambda: True):
+    """The distinct tile shapes the planner gives the case over the forced variants: {(bm, bn): plan}."""
+    out = {}
+    try:
+        for v in variants:
+            hip.set_igemm_variant(v)
+            if usable():
+                p = query(desc)
+                out.setdefault((p["bm"], p["bn"]), p)
+    finally:
+        hip.set_igemm_variant(-1)
+    return out
+
+
+def conv_operands(hip, case):
+    """One conv case -> (geometry without the tiles, raw buffers, Problem, descriptor)."""
+    n_img, H, W, cin, cout, stride, up, pao, split, cin2 = case
+    c = X.conv_case(n_img, H, W, cin, cout, stride, up, pao, cin2, 7, 0.5 if cin2 else 1.0)
+    p = c["problem"]
+    lda, lda2 = cin + 8, (cin2 + 16 if cin2 else 0)
+    geom = dict(M=n_img * p.Ho * p.Wo, N=cout, Cin=cin, Ktot=9 * cin + cin2, Hi=H, Wi=W, Ho=p.Ho, Wo=p.Wo, stride=stride, up=up,
+                pad=0 if pao else 1, lda=lda, nk1=p.nk1 if cin2 else NO_SEG2, Cin2=cin2, lda2=lda2)
+    w = c["w"].reshape(cout, cin, 9).transpose(0, 2, 1).reshape(cout, 9 * cin)          # rcdm_pack_conv3x3: [c_out][tap][c_in]
+    raw = dict(raw_a=padded_rows(c["x"].reshape(-1, cin), lda), raw_w=(np.concatenate([w, c["w2"]], axis=1) if cin2 else w).reshape(-1),
+               raw_a2=padded_rows(c["x2"].reshape(-1, cin2), lda2) if cin2 else None)
+    d = hip.ConvDesc(n_img, H, W, cin, cout, stride, up, lda, cout, cout, 7, c["rps"], cout, 1.0, split, pao, 0, cin2, lda2)
+    return geom, raw, p, d
+
+
+def check_tiles(tool, taps, plans, geom, raw, A_of, W_of, nk1=NO_SEG2, ph_rows=0):
+    assert plans
+    for (bm, bn), plan in sorted(plans.items()):
+        g = dict(geom, nk=plan["k_steps"], tilesM=plan["tiles_m"], tilesN=plan["tiles_n"])
+        rec = run_loader(tool, taps, bm, bn, g)
+        assert gathered_equals_model(rec, bm, bn, plan, raw["raw_a"], raw["raw_w"], A_of(plan["tiles_m"] * bm), W_of(plan["tiles_n"] * bn),
+                                     nk1, raw.get("raw_a2"), ph_rows), f"{bm}x{bn} tile: the gathered operands are not the model's"
+    return sorted(plans)
+
+
+@pytest.mark.parametrize("M,N,K", sorted({c[:3] for c in X.GEMM_CASES}))
+def test_loader_gemm_operands(hip, loader_tool, M, N, K):
+    c = X.gemm_case(M, N, K, 1, 1.0)
+    p = c["problem"]
+    d = hip.GemmDesc(M, N, K, K + 8, N + 16, N + 8, 1, c["rps"], N + 8, 1.0, 1)
+    geom = dict(M=M, N=N, Cin=K, Ktot=K, lda=K + 8)
+    raw = dict(raw_a=padded_rows(c["A"], K + 8), raw_w=c["W"].reshape(-1))
+    shapes = check_tiles(loader_tool, 1, tile_plans(hip, hip.gemm_plan_query, d), geom, raw,
+                         lambda rows: in_k_steps(p.A, p.steps, rows), lambda rows: in_k_steps(p.W, p.steps, rows)[None])
+    assert len(shapes) == 7, shapes       # 64x64, 128x64, 128x128, 160x160, 160x256, 160x320, 256x256
+
+
+@pytest.mark.parametrize("case", sorted({c[:8] + (1,) + c[9:] for c in X.CONV_CASES + X.ADD1X1_CASES}), ids=lambda c: "-".join(map(str, c)))
+def test_loader_conv_operands(hip, loader_tool, case):
+    geom, raw, p, d = conv_operands(hip, case)
+    shapes = check_tiles(loader_tool, 9, tile_plans(hip, hip.conv3x3_plan_query, d), geom, raw,
+                         lambda rows: in_k_steps(p.A, p.steps, rows), lambda rows: in_k_steps(p.W, p.steps, rows)[None], geom["nk1"])
+    assert len(shapes) == 7, shapes
+
+
+@pytest.mark.parametrize("n_img,H,W,cin,cout", sorted({c[:5] for c in X.UP2_CASES}))
+def test_loader_up2_operands(hip, loader_tool, n_img, H, W, cin, cout):
+    """The phase form (TAPS = 4) on the ping-pong tiles whose rows divide a phase."""
+    c = X.up2_case(n_img, H, W, cin, cout)
+    probs = c["problems"]
+    lda, src = cin + 8, n_img * H * W
+    d = hip.ConvDesc(n_img, H, W, cin, cout, 1, 2, lda, cout, 0, X.EPI_BIAS, 1, 0, 1.0, 1)
+    geom = dict(M=4 * src, N=cout, Cin=cin, Ktot=4 * cin, Hi=H, Wi=W, Ho=H, Wo=W, lda=lda, ph_rows=src)
+    raw = dict(raw_a=padded_rows(c["x"].reshape(-1, cin), lda), raw_w=X.up2_pack(c["w"]).reshape(-1))
+    plans = tile_plans(hip, hip.conv3x3_plan_query, d, (6, 7, 8), lambda: hip.conv3x3_up2_supported(d))
+    A = np.concatenate([q.A for q in probs])                      # virtual row = phase * ph_rows + source pixel
+    shapes = check_tiles(loader_tool, 4, plans, geom, raw, lambda rows: in_k_steps(A, probs[0].steps, rows),
+                         lambda rows: np.stack([in_k_steps(q.W, q.steps, rows) for q in probs]), ph_rows=src)
+    assert all(src % bm == 0 for bm, _ in shapes) and (160, 320) in shapes
+
+
+@pytest.mark.parametrize("tiles_m,tiles_n", [(1, 1), (3, 5), (9, 2), (17, 7), (8, 8), (1, 40)])
+def test_loader_tile_order_is_a_bijection(loader_tool, tiles_m, tiles_n):
+    for bm, bn in ((64, 64), (160, 320)):
+        rec = run_loader(loader_tool, 1, bm, bn, dict(M=tiles_m * bm, N=tiles_n * bn, Cin=64, Ktot=64, lda=64, nk=0, tilesM=tiles_m, tilesN=tiles_n))
+        assert (rec[:, 0] == 3).all() and (rec[:, 1] == np.arange(tiles_m * tiles_n)).all()
+        hit = sorted(zip(rec[:, 2].tolist(), rec[:, 3].tolist()))
+        assert hit == [(i * bm, j * bn) for i in range(tiles_m) for j in range(tiles_n)]        # every tile once
+
+
+def test_mutation_moved_border_tap(hip, loader_tool):
+    """One border tap moved: the tap above an image's first pixel, outside the image, reads the pixel itself instead."""
+    case = (6, 10, 6, 72, 72, 1, 0, 0, 1, 0)
+    geom, raw, p, d = conv_operands(hip, case)
+    plan = tile_plans(hip, hip.conv3x3_plan_query, d, (3,))[(64, 64)]
+    g = dict(geom, nk=plan["k_steps"], tilesM=plan["tiles_m"], tilesN=plan["tiles_n"])
+    rec = run_loader(loader_tool, 9, 64, 64, g)
+    check = lambda r: gathered_equals_model(r, 64, 64, plan, raw["raw_a"], raw["raw_w"], in_k_steps(p.A, p.steps, plan["tiles_m"] * 64),
+                                            in_k_steps(p.W, p.steps, plan["tiles_n"] * 64)[None])
+    assert check(rec)
+    piece = lambda ks: np.flatnonzero((rec[:, 0] == 0) & (rec[:, 1] == 0) & (rec[:, 2] == ks) & (rec[:, 3] == 0) & (rec[:, 5] == 0))[0]
+    border, below = piece(1), piece(4)        # k-steps 1 and 4: taps (0, 1) and (1, 1) of the first 64 channels
+    assert rec[border, 6] == -1 and rec[below, 6] >= 0
+    moved = rec.copy()
+    moved[border, 6] = rec[below, 6]
+    assert not check(moved)

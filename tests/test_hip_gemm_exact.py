@@ -10,6 +10,9 @@ Last, the f16 slabs at the edge of their range: partials that cancel (the error 
 reference's own partials) and partials or transform-domain values beyond 65504 (exactly right or non-finite, never finite
 and wrong)."""
 import contextlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +23,8 @@ from tests.guard import check_all
 from tests.test_hip_kernels import DEV, gin, gout, gvec, gw, ws
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 VARIANTS = list(range(1, 11))
 SLABS = [0, 1]
@@ -78,6 +83,11 @@ def partials_ok(key, problem, splits):
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_gemm(hiplib, M, N, K, epi, split, scale, variant, slab16):
     from rcdms_amd import hip
+    _gemm(hip, (M, N, K, epi, split, scale), variant, slab16)
+
+
+def _gemm(hip, case, variant, slab16):
+    M, N, K, epi, split, scale = case
     c = X.gemm_case(M, N, K, epi, scale)
     lda, ldc, ldr, ldt = K + 8, N + 16, N + 8, N + 8
     d = hip.GemmDesc(M, N, K, lda, ldc, ldr, epi, c["rps"], ldt, scale, split)
@@ -226,6 +236,38 @@ def test_conv_taps_gather(hiplib, up):
     exact(P[:, :9 * cout], planes, "tap planes: ")
     exact(out[:, :cout], c["ref"])
     check_all(out, P, xd, W9d, bd)
+
+
+# ---- RCDM_PP_ROTATE=1: the ping-pong kernel's per-block k rotation in front of the shared k-step decode ---------------------
+# Split GEMM, split conv and second-input cases of the lists above, and one GEMM and one conv with more than eight row tiles:
+# the rotation of a block is its position in its XCD's run of tiles (blockIdx.x >> 3), zero for every block of the small cases.
+ROTATED_GEMMS = [(161, 168, 704, 1, 3, 1.0), (2305, 168, 704, 1, 3, 1.0)]
+ROTATED_CONVS = [(2, 8, 8, 320, 320, 1, 0, 0, 4, 0), (2, 8, 8, 320, 320, 1, 0, 0, 4, 640), (40, 8, 8, 128, 64, 1, 0, 0, 1, 0)]
+
+
+def rotated_child():
+    """Runs in a process of its own (the switch is latched at the first ping-pong launch)."""
+    assert os.environ.get("RCDM_PP_ROTATE") == "1"
+    from rcdms_amd import hip
+    hip.load()
+    for variant in (6, 8):
+        for slab16 in SLABS:
+            for case in ROTATED_GEMMS:
+                _gemm(hip, case, variant, slab16)
+            for case in ROTATED_CONVS:
+                _conv(hip, case, variant, slab16)
+    print("rotated: ok")
+
+
+def test_pingpong_rotated_k_order(hiplib):
+    """Bit for bit in any k order: integer sums below 2^24 are exact, and the rotation stays inside a split, so every slab
+    holds the same set of k-steps."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RCDM_") or k == "RCDM_LIB"}
+    env["RCDM_PP_ROTATE"] = "1"
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-m", "tests.test_hip_gemm_exact", "--rotated"]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0 and text.strip().endswith("rotated: ok"), text[-4000:]
 
 
 # ---- the *_gnstat entries: the output rows (their statistics keep their bit-identity test in tests/test_hip_kernels.py) -------
@@ -394,3 +436,8 @@ def test_wino_input_transform_out_of_range(hiplib, wino16):
     torch.cuda.synchronize()
     exact(out9, want, "nine-tap form: ")
     check_all(out9, wp, xd, w32, bd)
+
+
+if __name__ == "__main__":
+    if "--rotated" in sys.argv:
+        rotated_child()
