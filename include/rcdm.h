@@ -52,6 +52,9 @@ extern "C" {
                              * MLP activation of the SD-1.5 CLIP text encoder.  rcdm_gemm only (every tile family and the split-K
                              * reduce); not with GELU / GEGLU (RCDM_EINVAL); rcdm_gemm_ln / _lnx / *_gnstat / rcdm_conv3x3*:
                              * RCDM_ESHAPE */
+#define RCDM_EPI_RELU 64     /* out = max(v, 0), v = acc + bias; a NaN stays NaN, -0.0 gives +0.0.  rcdm_conv2d only (where the
+                             * only other bit allowed is RCDM_EPI_BIAS); every other entry point that takes an epilogue
+                             * refuses it, and any bit this list does not name, with RCDM_ESHAPE */
 
 int rcdm_version(void);
 /* last HIP error code seen by this library on this thread (0 = none) and its string */
@@ -1120,6 +1123,73 @@ size_t rcdm_clip_tokenize_workspace_bytes(const rcdm_tokenize_desc* d);
 int rcdm_clip_tokenize(const rcdm_tokenize_desc* d, const void* text, const int32_t* offsets, const int32_t* byte_ids,
                        const rcdm_tok_added* added, const rcdm_tok_pair* pairs, int64_t* input_ids, int64_t* attention_mask,
                        int32_t* lengths, int32_t* pool_index, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * General conv2d, pools, bilinear frames: what an Inception-v3 forward (torchvision.models.inception_v3, pytorch-fid's
+ * FIDInceptionA/C/E_1/E_2) needs beyond the kernels above; rcdms_amd/inception.py is the caller.  Activations are the f16
+ * pixel rows [n * h * w][ld] of this header, so a block's torch.cat(branches, 1) is a column window per branch of one wider
+ * buffer (out = buffer + column offset, ldc = the buffer's row stride).  Output sides, conv and pools alike:
+ *   h_out = (h_in + 2 pad_h - kh) / stride_h + 1 (floor), likewise w_out; below 1 is RCDM_ESHAPE.
+ * Every check is made before anything is launched: null pointers, sizes <= 0, ld below the channel count, a pointer that is
+ * not 16-byte aligned give RCDM_EINVAL, a shape limit RCDM_ESHAPE.  No atomics: equal inputs give equal bits.  Row and
+ * byte offsets are 64-bit (n_img * h_out * w_out itself must stay below 2^31 - 64).
+ *
+ * rcdm_conv2d: out[m][o] = epi( sum_{ky,kx,c} in[img, oy stride_h - pad_h + ky, ox stride_w - pad_w + kx][c] * W[o][(ky kw + kx) c_in + c] ),
+ *   m = (img, oy, ox); taps outside the image are zeros.  W f16 [c_out][kh * kw * c_in] = torch weight.permute(0, 2, 3, 1),
+ *   the convention of rcdm_conv3x3.  fp32 accumulation on v_mfma_f32_16x16x32_f16 (64 x 64 output tile per 4-wave block, k in
+ *   steps of 32 in ascending order), epilogue in fp32, one rounding to f16.  epilogue: RCDM_EPI_BIAS (fp32 [c_out]) and / or
+ *   RCDM_EPI_RELU; any other bit is RCDM_ESHAPE.  Limits (RCDM_ESHAPE): c_in % 8 == 0 (a 16-byte operand chunk never
+ *   straddles a tap: a 3-channel image is padded to 8 with zeros), c_out % 8 == 0, lda % 8 == 0, ldc % 8 == 0, kh, kw <= 7,
+ *   pad < kernel per axis, strides 1 or 2, sides <= 8192.
+ * rcdm_pool2d: window <= 3 x 3, strides 1 or 2, 2 pad <= window per axis (so no window is all padding), c % 8 == 0,
+ *   ld_in % 8 == 0, ld_out % 8 == 0.  Taps are visited ky-major then kx; padding is skipped, never read.
+ *     RCDM_POOL_MAX               the largest in-image tap (exact; a NaN in the window is the result)
+ *     RCDM_POOL_AVG_INCLUDE_PAD   fp32 sum of the in-image taps in that order / (kh kw), fp32 division, rounded once
+ *     RCDM_POOL_AVG_EXCLUDE_PAD   the same sum / the number of in-image taps
+ * rcdm_global_avgpool: out_f32[img][ch] = (((0 + x[0][ch]) + x[1][ch]) + ... + x[rows_per_img - 1][ch]) / rows_per_img over
+ *   the rows of image img (in + img * rows_per_img * ld): ONE fp32 accumulator per channel, the rows added in ascending
+ *   order, one fp32 division by (float)rows_per_img at the end.  c % 8 == 0, ld % 8 == 0, ldo % 4 == 0.
+ * rcdm_image_bilinear_rows: n uint8 HWC frames (channels == 3; src_pitch / src_stride bytes between rows / frames, as
+ *   rcdm_resample_desc) -> f16 rows [n * out_h * out_w][ld]: channel ch of the output is channel (flip_channels ? 2 - ch : ch)
+ *   of torch.nn.functional.interpolate(x / 255, (out_h, out_w), mode="bilinear", align_corners=False) (no antialias: the FID
+ *   definition of pytorch-fid, not Pillow's resampler) times scale[ch] plus shift[ch] (two roundings), rounded to f16; channels
+ *   3 .. c_pad are zeros (c_pad % 8 == 0, 8 <= c_pad <= ld, ld % 8 == 0).  All fp32, per axis
+ *     s = max(fma((float)in / out, o + 0.5, -0.5), 0)  (one rounding, as torch's CPU build evaluates it; nothing else is contracted),
+ *     i0 = min((int)s, in - 1), i1 = min(i0 + 1, in - 1), l1 = s - i0, l0 = 1 - l1
+ *   value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11) with v = u8 / 255 (a division).  Equal sizes give
+ *   l1 = 0 on both axes, so the result is exactly f16((u8 / 255) * scale + shift).  Sides <= 8192 (RCDM_ESHAPE).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_img, h_in, w_in;
+  int32_t c_in, c_out;
+  int32_t kh, kw, stride_h, stride_w, pad_h, pad_w;
+  int32_t lda, ldc;               /* row strides of in / out in elements */
+  int32_t epilogue;               /* RCDM_EPI_BIAS | RCDM_EPI_RELU */
+} rcdm_conv2d_desc;
+int rcdm_conv2d(const rcdm_conv2d_desc* d, const void* in, const void* W, const float* bias, void* out, void* stream);
+
+#define RCDM_POOL_MAX 0
+#define RCDM_POOL_AVG_INCLUDE_PAD 1
+#define RCDM_POOL_AVG_EXCLUDE_PAD 2
+typedef struct {
+  int32_t n_img, h_in, w_in, c;
+  int32_t kh, kw, stride_h, stride_w, pad_h, pad_w;
+  int32_t ld_in, ld_out;
+  int32_t mode;                   /* RCDM_POOL_* */
+} rcdm_pool2d_desc;
+int rcdm_pool2d(const rcdm_pool2d_desc* d, const void* in, void* out, void* stream);
+int rcdm_global_avgpool(int32_t n_img, int32_t rows_per_img, int32_t c, const void* in, int64_t ld, float* out_f32, int64_t ldo,
+                        void* stream);
+
+typedef struct {
+  int64_t src_pitch, src_stride;   /* bytes between source rows / source frames */
+  int32_t n, channels;             /* channels == 3 */
+  int32_t in_h, in_w, out_h, out_w;
+  int32_t flip_channels;
+  int32_t ld, c_pad;
+  float scale[3], shift[3];        /* per OUTPUT channel */
+} rcdm_bilinear_desc;
+int rcdm_image_bilinear_rows(const rcdm_bilinear_desc* d, const void* src_u8, void* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.

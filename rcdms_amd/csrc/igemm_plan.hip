@@ -410,6 +410,8 @@ int check_common(const IgemmArgs& a) {
   if (!a.A || !a.W || !a.out) return RCDM_EINVAL;
   if (a.M <= 0 || a.N <= 0 || a.Cin <= 0) return RCDM_EINVAL;
   if ((a.Cin & 7) || (a.N & 7) || (a.lda & 7) || (a.ldc & 7)) return RCDM_ESHAPE;
+  if (a.epi & ~(RCDM_EPI_BIAS | RCDM_EPI_ROWVEC | RCDM_EPI_RESIDUAL | RCDM_EPI_GEGLU | RCDM_EPI_GELU | RCDM_EPI_QUICK_GELU))
+    return RCDM_ESHAPE;   // a bit these kernels do not know (RCDM_EPI_RELU is rcdm_conv2d's)
   if ((a.epi & RCDM_EPI_BIAS) && !a.bias) return RCDM_EINVAL;
   if ((a.epi & RCDM_EPI_ROWVEC) && (!a.rowvec || a.rows_per_sample <= 0 || (a.ldt & 3))) return RCDM_EINVAL;
   if ((a.epi & RCDM_EPI_RESIDUAL) && (!a.res || (a.ldr & 7))) return RCDM_EINVAL;

@@ -10,7 +10,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RCDM_LIB") or os.path.join(_HERE, "lib", "librcdm_hip.so")  # RCDM_LIB: kernel experiments
 
-EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU, EPI_GELU, EPI_QUICK_GELU = 1, 2, 4, 8, 16, 32
+EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU, EPI_GELU, EPI_QUICK_GELU, EPI_RELU = 1, 2, 4, 8, 16, 32, 64
 
 _ERR = {-1: "RCDM_EINVAL", -2: "RCDM_ESHAPE", -3: "RCDM_ELAUNCH", -4: "RCDM_EWORKSPACE", -5: "RCDM_ECOMM"}
 
@@ -94,6 +94,25 @@ class FramesU8Desc(C.Structure):
                 ("channels", C.c_int32), ("src_kind", C.c_int32), ("ld", C.c_int32)]
 
 
+class Conv2dDesc(C.Structure):
+    _fields_ = [("n_img", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32),
+                ("kh", C.c_int32), ("kw", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32),
+                ("pad_h", C.c_int32), ("pad_w", C.c_int32), ("lda", C.c_int32), ("ldc", C.c_int32), ("epilogue", C.c_int32)]
+
+
+class Pool2dDesc(C.Structure):
+    _fields_ = [("n_img", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("c", C.c_int32),
+                ("kh", C.c_int32), ("kw", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32),
+                ("pad_h", C.c_int32), ("pad_w", C.c_int32), ("ld_in", C.c_int32), ("ld_out", C.c_int32), ("mode", C.c_int32)]
+
+
+class BilinearDesc(C.Structure):
+    _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("n", C.c_int32), ("channels", C.c_int32),
+                ("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("flip_channels", C.c_int32), ("ld", C.c_int32), ("c_pad", C.c_int32),
+                ("scale", C.c_float * 3), ("shift", C.c_float * 3)]
+
+
 class PngDesc(C.Structure):
     _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("n", C.c_int32),
                 ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32)]
@@ -158,6 +177,7 @@ PNG_STATUS = {1: "RCDM_PNG_EZLIB", 2: "RCDM_PNG_ETRUNC", 3: "RCDM_PNG_EBLOCK", 4
 IMAGE_TILE = 32                                         # RCDM_IMAGE_TILE
 IMAGE_U8, IMAGE_F32_NCHW, IMAGE_F16_ROWS = 0, 1, 2      # ResampleDesc.mode
 FRAMES_F16_ROWS, FRAMES_F32_NCHW = 0, 1                 # FramesU8Desc.src_kind
+POOL_MAX, POOL_AVG_INCLUDE_PAD, POOL_AVG_EXCLUDE_PAD = 0, 1, 2   # Pool2dDesc.mode
 
 # every symbol include/rcdm.h declares: name -> (restype, argtypes)
 _P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -231,6 +251,10 @@ SYMBOLS = {
     "rcdm_image_resample_lds_bytes": (_SZ, [C.POINTER(ResampleDesc)]),
     "rcdm_image_resample": (C.c_int, [C.POINTER(ResampleDesc), _P, _P, _P, _P, _P, _P, _P]),
     "rcdm_frames_to_u8": (C.c_int, [C.POINTER(FramesU8Desc), _P, _P, _P]),
+    "rcdm_conv2d": (C.c_int, [C.POINTER(Conv2dDesc), _P, _P, _P, _P, _P]),
+    "rcdm_pool2d": (C.c_int, [C.POINTER(Pool2dDesc), _P, _P, _P]),
+    "rcdm_global_avgpool": (C.c_int, [_I, _I, _I, _P, C.c_int64, _P, C.c_int64, _P]),
+    "rcdm_image_bilinear_rows": (C.c_int, [C.POINTER(BilinearDesc), _P, _P, _P]),
     "rcdm_png_bound": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_encode": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
@@ -581,6 +605,24 @@ def image_resample(desc, src, kx, bx, ky, by, dst, stream=None):
 
 def frames_to_u8(desc, src, dst, stream=None):
     _check(load().rcdm_frames_to_u8(C.byref(desc), src, dst, stream_ptr() if stream is None else stream), "rcdm_frames_to_u8")
+
+
+def conv2d(desc, x, W, bias, out, stream=None):
+    _check(load().rcdm_conv2d(C.byref(desc), x, W, bias, out, stream_ptr() if stream is None else stream), "rcdm_conv2d")
+
+
+def pool2d(desc, x, out, stream=None):
+    _check(load().rcdm_pool2d(C.byref(desc), x, out, stream_ptr() if stream is None else stream), "rcdm_pool2d")
+
+
+def global_avgpool(n_img, rows_per_img, c, x, ld, out, ldo, stream=None):
+    _check(load().rcdm_global_avgpool(n_img, rows_per_img, c, x, ld, out, ldo, stream_ptr() if stream is None else stream),
+           "rcdm_global_avgpool")
+
+
+def image_bilinear_rows(desc, src, dst, stream=None):
+    _check(load().rcdm_image_bilinear_rows(C.byref(desc), src, dst, stream_ptr() if stream is None else stream),
+           "rcdm_image_bilinear_rows")
 
 
 def png_bound(desc):

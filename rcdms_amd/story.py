@@ -104,6 +104,7 @@ class StoryResult:
 
 
 METRICS = ("ssim", "psnr", "clip_i")
+FEATURE_SOURCES = ("clip", "inception")
 AUTOREG_OUTPUTS = ("tensor", "uint8", "png")
 
 
@@ -153,10 +154,12 @@ class StoryRunner:
     prior_pipe: Seq_Inpaint_Prior_Pipeline; stage2_pipe: RCDMsPipeline (None: stage 1 only); image_encoder: the CLIP vision
     tower with projection (`.image_embeds`, `.last_hidden_state`); clip_processor: frames -> pixel values (default
     rcdms_amd.image.ClipImageProcessor at the encoder's image size); frame_transform: frames -> stage-2 source frames in
-    [-1, 1] (default rcdms_amd.image.FrameTransform at the UNet's sample size)."""
+    [-1, 1] (default rcdms_amd.image.FrameTransform at the UNet's sample size); inception: an
+    rcdms_amd.inception.InceptionV3Features (uint8 frames -> (n, 2048) fp32), the extractor of feature_source="inception"."""
 
-    def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None):
+    def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None, inception=None):
         self.prior_pipe, self.stage2_pipe, self.image_encoder = prior_pipe, stage2_pipe, image_encoder
+        self.inception = inception
         if clip_processor is None:
             from .image import ClipImageProcessor
             size = int(image_encoder.config.image_size)
@@ -206,7 +209,8 @@ class StoryRunner:
     def __call__(self, frames, texts, mode="continue", autoreg=False, num_inference_steps=50, prior_steps=25,
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
                  save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=(),
-                 stage2_autoreg=False, frames_dir=None, grid_dir=None, feature_stats=None, feature_banks=None):
+                 stage2_autoreg=False, frames_dir=None, grid_dir=None, feature_stats=None, feature_banks=None,
+                 feature_source="clip"):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
@@ -222,6 +226,11 @@ class StoryRunner:
         feature_banks: (generated, reference), two rcdms_amd.kid.FeatureBank of the embedding width: the same rows, kept rather
         than summed, for a kernel distance (kernel_distance; a CLIP-KID).  The same forward, the same requirements.  None: nothing
         more is launched.
+        feature_source: where the rows of feature_stats / feature_banks come from.  "clip" (default): the CLIP embeddings, as
+        above.  "inception": the runner's `inception` extractor — `generated` receives inception(the 5 S generated uint8
+        frames), `reference` inception(the five given uint8 frames of every story), 2048 wide: the inputs of an Inception FID /
+        KID.  The CLIP forward over the generated frames then runs only when "clip_i" is asked for as well.  Without an extractor,
+        or with an output type that leaves no uint8 frames, "inception" is a ValueError before anything is launched.
         stage2_autoreg: the stage-2 driver's --autoreg loop (stage2…:304-362) for the S stories, independent of `autoreg`
         (stage 1's loop): five stage-2 calls at batch S, pass i keeping frame i of every story —
           pass 0: the call of stage2_autoreg=False (given frame 0 seen, image_embeds_1 its hidden state, proj_embeds_0
@@ -245,6 +254,13 @@ class StoryRunner:
                 raise ValueError(f"metric {m!r}: any of {METRICS}")
         if mode not in ("continue", "visualization"):
             raise ValueError("check mode")                                      # stage1…:180
+        if feature_source not in FEATURE_SOURCES:
+            raise ValueError(f"feature_source {feature_source!r}: one of {FEATURE_SOURCES}")
+        if feature_source == "inception":
+            if self.inception is None:
+                raise ValueError('feature_source="inception" needs an extractor: build the runner with inception=InceptionV3Features(...)')
+            if output_type != "uint8" and not stage2_autoreg:
+                raise ValueError(f'feature_source="inception" reads uint8 frames: pass output_type="uint8", not {output_type!r}')
         if stage2 is None:
             stage2 = mode == "continue" and self.stage2_pipe is not None
         if stage2 and mode == "visualization":
@@ -344,7 +360,7 @@ class StoryRunner:
         figures = {}
         if metrics or feature_stats is not None or feature_banks is not None:
             figures = self.story_metrics(frames_u8 if stage2_autoreg else videos, frames, target, metrics, feature_stats,
-                                         feature_banks)
+                                         feature_banks, feature_source)
         return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures,
                            frames_u8=frames_u8 if stage2_autoreg else None)
 
@@ -390,11 +406,20 @@ class StoryRunner:
         r = resampler(flat.shape[1], flat.shape[2], ft.height, ft.width, ft.resample, None, flat.device)
         return r.to_uint8(flat, ft.flip_channels).view(S, FRAMES, ft.height, ft.width, 3)
 
-    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None, feature_banks=None):
+    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None, feature_banks=None, feature_source="clip"):
         """videos: uint8 (S, 5, H, W, 3) as stage 2 returns them; frames: the given uint8 (S, 5, Hs, Ws, 3) on the device.
         -> {name: (S, 5) tensor} for the names in `metrics`.  feature_stats: (generated, reference) FeatureStats that take the
-        embeddings of `videos` and target_embeds; feature_banks: (generated, reference) FeatureBanks that keep the same rows."""
+        embeddings of `videos` and target_embeds; feature_banks: (generated, reference) FeatureBanks that keep the same rows.
+        feature_source="inception": both pairs receive the runner's Inception features of `videos` and of `frames` instead."""
         from .metrics import frame_metrics
+        if feature_source not in FEATURE_SOURCES:
+            raise ValueError(f"feature_source {feature_source!r}: one of {FEATURE_SOURCES}")
+        wants_rows = feature_stats is not None or feature_banks is not None
+        inception = feature_source == "inception"
+        if inception and self.inception is None:
+            raise ValueError('feature_source="inception" needs an extractor: build the runner with inception=InceptionV3Features(...)')
+        if inception and wants_rows and videos.dtype != torch.uint8:
+            raise ValueError(f'feature_source="inception" reads uint8 frames, got {videos.dtype}')
         S = videos.shape[0]
         out = {}
         if "ssim" in metrics or "psnr" in metrics:
@@ -403,16 +428,21 @@ class StoryRunner:
                 out["ssim"] = fm.ssim.view(S, FRAMES)
             if "psnr" in metrics:
                 out["psnr"] = fm.psnr.view(S, FRAMES)
-        if "clip_i" in metrics or feature_stats is not None or feature_banks is not None:
+        if "clip_i" in metrics or (wants_rows and not inception):
             e = self.image_encoder(self._pixels(videos.reshape(S * FRAMES, *videos.shape[2:]))).image_embeds
+        if wants_rows and inception:
+            gen_rows = self.inception(videos.reshape(S * FRAMES, *videos.shape[2:]))
+            ref_rows = self.inception(frames.reshape(S * FRAMES, *frames.shape[2:]))
+        elif wants_rows:
+            gen_rows, ref_rows = e.reshape(S * FRAMES, -1), target_embeds.reshape(S * FRAMES, -1)
         if feature_stats is not None:
             generated, reference = feature_stats
-            generated.update(e.reshape(S * FRAMES, -1))
-            reference.update(target_embeds.reshape(S * FRAMES, -1))
+            generated.update(gen_rows)
+            reference.update(ref_rows)
         if feature_banks is not None:
             generated, reference = feature_banks
-            generated.append(e.reshape(S * FRAMES, -1))
-            reference.append(target_embeds.reshape(S * FRAMES, -1))
+            generated.append(gen_rows)
+            reference.append(ref_rows)
         if "clip_i" in metrics:
             out["clip_i"] = torch.nn.functional.cosine_similarity(e.reshape(S, FRAMES, -1).float(), target_embeds.float(), dim=-1)
         return out
