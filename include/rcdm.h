@@ -1065,6 +1065,71 @@ int rcdm_poly_gram_f64(const rcdm_mmd_desc* d, const void* x, const void* y, con
                        int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Manifold figures: improved precision and recall (Kynkaanniemi et al., 2019) and density and coverage (Naeem et al., 2020)
+ * over stored feature rows — whether a model lost fidelity or lost diversity, which one distance cannot say.
+ * csrc/prdc_core.h holds the arithmetic, shared with tools/prdc_host.cpp.  Restated from the papers; not pinned against prdc,
+ * torch-fidelity or torchmetrics.
+ *   inputs      real rows x[nx][ldx] and generated rows y[ny][ldy], RCDM_FSTATS_F32 or _F16 (columns d..ld are never read),
+ *               widened exactly.  k = nearest_k, an integer in 1 .. 16; nx, ny >= k + 1.
+ *   distance    D2(a, b) = max(0, (|a|^2 + |b|^2) - 2 <a, b>) in float64 with no contraction.  |a|^2 is summed from the exact
+ *               products through the fixed sum of the Fréchet entries (256 strided partial sums, then the tree); the dot is
+ *               summed in float64 on the matrix pipe.  Every comparison is made on squared distances: no square root.
+ *   radius      rX2[i] = the k-th smallest of { D2(x_i, x_j) : j != i }, counted with multiplicity.  Self-exclusion goes BY
+ *               POSITION, as the kernel distance's diagonal mask does: a repeated row is its twin's neighbour at distance 0.
+ *               rY2 the same over y.
+ *   balls       closed (<=) in all four figures:
+ *                 fake_count[j] = #{ i : D2(x_i, y_j) <= rX2[i] }
+ *                 real_hit[i]   = 1 if some j has D2(x_i, y_j) <= rY2[j], else 0
+ *                 real_min2[i]  = min_j D2(x_i, y_j)
+ *   figures     precision = #{ j : fake_count[j] > 0 } / ny          recall   = sum_i real_hit[i] / nx
+ *               density   = sum_j fake_count[j] / (k ny)              coverage = #{ i : real_min2[i] <= rX2[i] } / nx
+ *               out[4] = the four NUMERATORS as int64, in the order precision, recall, density, coverage; the divisions are
+ *               the caller's, once, in float64.
+ *   deviation   the prdc package compares strictly; the two rules differ on exact ties only.
+ *   masks       positions outside a set, and the position-diagonal of the radius sweep, are masked in the epilogue: a padded
+ *               row enters the matrix pipe as the zero vector, which is a real point near a centred cloud — zero operands mask
+ *               nothing.
+ *   order       every reduction after the distances is a k-smallest selection, an integer sum, an or or a minimum: the same
+ *               input gives the same bits whatever col_chunks is.  No atomics.
+ *   rcdm_row_norms2_f64   out[n] = |x_i|^2 in float64, the fixed sum; one launch.
+ *   rcdm_knn_radii2       r2[n].  Grid (row strips of 64, column chunks); each chunk keeps k candidates per row in the workspace,
+ *                         a second launch merges them.  col_chunks = 0: the library chooses enough chunks to fill 256 compute
+ *                         units at this n (eight workgroups each, at most one chunk per tile column); 1 .. 1024: the caller's (more chunks than tile columns is allowed).  The distance
+ *                         matrix never reaches memory.
+ *   rcdm_prdc_counts      rx2[nx], ry2[ny]: the radii (of rcdm_knn_radii2 or the caller's own).  out: int64[4]; fake_count:
+ *                         int32[ny]; real_hit: int32[nx]; real_min2: double[nx]; all caller-owned, all fully written.  One sweep
+ *                         of the nx x ny tiles, a fold launch and a last launch of one workgroup.  x == y is allowed.
+ *   *_workspace_bytes     radii: (1 + chunks k) n doubles.  Counts: nx + ny + chunks nx doubles, 4 int64 per 256 of
+ *                         max(nx, ny), chunks nx int32 and ceil(nx / 64) ny bytes, each part rounded up to 8 bytes.  0 for a
+ *                         refused descriptor.
+ * RCDM_EINVAL: a null descriptor or pointer; d < 1, n < 1, ld < d, k outside 1 .. 16, n < k + 1, col_chunks outside 0 .. 1024,
+ * an unknown dtype, flags != 0, a misaligned pointer (rows at their element size, int32 at 4, double / int64 / workspace at 8).
+ * RCDM_ESHAPE: d > 4096, n > 65536.  RCDM_EWORKSPACE: workspace null or short.  All checked before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t ld;                      /* elements between rows, >= d */
+  int32_t n, d;                    /* rows, features per row */
+  int32_t k;                       /* nearest_k, 1 .. 16 */
+  int32_t dtype;                   /* RCDM_FSTATS_* */
+  int32_t col_chunks;              /* 0: the library chooses */
+  uint32_t flags;                  /* 0 */
+} rcdm_knn_desc;
+typedef struct {
+  int64_t ldx, ldy;                /* elements between rows of x and of y, >= d */
+  int32_t nx, ny, d;               /* real rows, generated rows, features per row */
+  int32_t dtype;                   /* RCDM_FSTATS_* */
+  int32_t col_chunks;              /* 0: the library chooses */
+  uint32_t flags;                  /* 0 */
+} rcdm_prdc_desc;
+int rcdm_row_norms2_f64(const void* x, int32_t n, int32_t d, int64_t ld, int32_t dtype, double* out, void* stream);
+size_t rcdm_knn_radii2_workspace_bytes(const rcdm_knn_desc* d);
+int rcdm_knn_radii2(const rcdm_knn_desc* d, const void* x, double* r2, void* workspace, size_t workspace_bytes, void* stream);
+size_t rcdm_prdc_counts_workspace_bytes(const rcdm_prdc_desc* d);
+int rcdm_prdc_counts(const rcdm_prdc_desc* d, const void* x, const void* y, const double* rx2, const double* ry2, int64_t* out,
+                     int32_t* fake_count, int32_t* real_hit, double* real_min2, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
  * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
  * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the

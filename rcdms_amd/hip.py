@@ -153,6 +153,16 @@ class MmdDesc(C.Structure):
                 ("gamma", C.c_double), ("coef0", C.c_double), ("flags", C.c_uint32)]
 
 
+class KnnDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("n", C.c_int32), ("d", C.c_int32), ("k", C.c_int32), ("dtype", C.c_int32),
+                ("col_chunks", C.c_int32), ("flags", C.c_uint32)]
+
+
+class PrdcDesc(C.Structure):
+    _fields_ = [("ldx", C.c_int64), ("ldy", C.c_int64), ("nx", C.c_int32), ("ny", C.c_int32), ("d", C.c_int32),
+                ("dtype", C.c_int32), ("col_chunks", C.c_int32), ("flags", C.c_uint32)]
+
+
 class TokAdded(C.Structure):
     _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
 
@@ -167,6 +177,7 @@ TOK_MAX_CAPTION, TOK_MAX_ADDED, TOK_MAX_ROWS, TOK_MAX_ADDED_LEN, TOK_MAX_RANK, T
 FSTATS_F32, FSTATS_F16 = 0, 1                            # FStatsDesc.dtype
 FRECHET_MAX_DIM = 4096
 KID_MAX_M, KID_MAX_SUBSETS, KID_MAX_DEGREE = 65536, 65535, 8   # kid::MAX_M, MAX_SUBSETS, MAX_DEGREE (d: FRECHET_MAX_DIM)
+PRDC_MAX_K, PRDC_MAX_N, PRDC_MAX_CHUNKS = 16, 65536, 1024      # prdc::MAX_K, MAX_N, MAX_CHUNKS (d: FRECHET_MAX_DIM)
 CHOLESKY_NB = 16                                          # fr::CHOL_NB, the panel width CholeskyDesc.nb = 0 stands for
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
@@ -278,6 +289,11 @@ SYMBOLS = {
     "rcdm_poly_mmd_workspace_bytes": (_SZ, [C.POINTER(MmdDesc)]),
     "rcdm_poly_mmd": (C.c_int, [C.POINTER(MmdDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_poly_gram_f64": (C.c_int, [C.POINTER(MmdDesc), _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rcdm_row_norms2_f64": (C.c_int, [_P, _I, _I, C.c_int64, _I, _P, _P]),
+    "rcdm_knn_radii2_workspace_bytes": (_SZ, [C.POINTER(KnnDesc)]),
+    "rcdm_knn_radii2": (C.c_int, [C.POINTER(KnnDesc), _P, _P, _P, _SZ, _P]),
+    "rcdm_prdc_counts_workspace_bytes": (_SZ, [C.POINTER(PrdcDesc)]),
+    "rcdm_prdc_counts": (C.c_int, [C.POINTER(PrdcDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -733,6 +749,27 @@ def poly_mmd(desc, x, y, ix, iy, out, workspace, workspace_bytes, stream=None):
 
 def poly_gram_f64(desc, x, y, ix, iy, out, ldo, stream=None):
     _check(load().rcdm_poly_gram_f64(C.byref(desc), x, y, ix, iy, out, ldo, _st(stream)), "rcdm_poly_gram_f64")
+
+
+def row_norms2_f64(x, n, d, ld, dtype, out, stream=None):
+    _check(load().rcdm_row_norms2_f64(x, n, d, ld, dtype, out, _st(stream)), "rcdm_row_norms2_f64")
+
+
+def knn_radii2_workspace_bytes(desc):
+    return int(load().rcdm_knn_radii2_workspace_bytes(C.byref(desc)))
+
+
+def knn_radii2(desc, x, r2, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_knn_radii2(C.byref(desc), x, r2, workspace, workspace_bytes, _st(stream)), "rcdm_knn_radii2")
+
+
+def prdc_counts_workspace_bytes(desc):
+    return int(load().rcdm_prdc_counts_workspace_bytes(C.byref(desc)))
+
+
+def prdc_counts(desc, x, y, rx2, ry2, out, fake_count, real_hit, real_min2, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_prdc_counts(C.byref(desc), x, y, rx2, ry2, out, fake_count, real_hit, real_min2, workspace, workspace_bytes,
+                                   _st(stream)), "rcdm_prdc_counts")
 
 
 def frame_metrics_workspace_bytes(desc):

@@ -6,6 +6,7 @@ squared maximum mean discrepancy under the polynomial kernel k(x, y) = (gamma <x
 the features and reported as a mean and a spread.  It needs no covariance and no factorisation — but it needs the rows:
 
   FeatureBank       keeps feature rows on the device (FeatureStats keeps only moments); StoryRunner(..., feature_banks=...) fills two.
+                    radii2(k) caches the k-nearest-neighbour radii of rcdms_amd.prdc.
   draw_subsets      this project's rule for the random subsets (numpy's RandomState, see there).
   polynomial_mmd    Sxx, Syy, Sxy and mmd^2 of every subset: one launch of the tile kernel (float64 matrix pipe, rows gathered
                     through the index lists) and one of the reduce (csrc/kid.hip; csrc/kid_core.h has the definition).
@@ -51,6 +52,7 @@ class FeatureBank:
         self.dtype = dtype
         self.n = 0
         self._buf = None           # (capacity, d), the first n rows live
+        self._radii2 = {}          # k -> (n,) float64 squared k-nearest-neighbour radii of the rows held (radii2)
 
     def append(self, feats):
         """feats: (..., d) float32 or float16 on this device, rows of any pitch.  float16 rows into a float32 bank are widened
@@ -79,6 +81,7 @@ class FeatureBank:
             self._buf = buf
         self._buf[self.n:need] = x               # copy_ widens float16 exactly
         self.n = need
+        self._radii2.clear()
         return self
 
     def __len__(self):
@@ -92,7 +95,17 @@ class FeatureBank:
 
     def clear(self):
         self.n = 0
+        self._radii2.clear()
         return self
+
+    def radii2(self, k):
+        """(n,) float64 device tensor: the squared distance of every row to its k-th nearest other row (rcdms_amd.prdc), kept per
+        k until the next append or clear — a reference set is swept once, as FeatureStats keeps its factor."""
+        from . import prdc
+        k = prdc._k(k)
+        if k not in self._radii2:
+            self._radii2[k] = prdc._radii2(prdc._rows(self.rows(), "bank", k), k)
+        return self._radii2[k]
 
     def stats(self):
         """A FeatureStats of the same rows (for frechet_distance)."""
