@@ -1130,6 +1130,55 @@ int rcdm_prdc_counts(const rcdm_prdc_desc* d, const void* x, const void* y, cons
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scores from logits: the multi-label counts behind Char-F1 / Frm-Acc (the character classifier of the story-visualisation
+ * papers) and the Inception Score, over classifier logits that are already on the device.  csrc/scores_core.h holds every
+ * rule and every summation order, shared with tools/scores_host.cpp.  Restated from the definitions; the label figures are
+ * held against scikit-learn, the Inception Score is not pinned against torch-fidelity / torchmetrics.
+ *   label counts  logits[n][ld_logits]: RCDM_FSTATS_F32 or _F16; labels[n][ld_labels]: bytes; classes = 1 .. 64 columns of
+ *                 each are read.  Prediction: logit > threshold[c], strictly, in float32 (thresholds: float32[classes], or
+ *                 null: all 0.0); a NaN predicts 0; a label is 1 when its byte is non-zero.
+ *     state       int64[rcdm_label_state_len(classes)] = [n | tp, fp, fn per class | H[t][e], (classes + 1)^2], H counting
+ *                 the rows with t true positives and e false positives + false negatives.  rcdm_label_counts ADDS its n rows
+ *                 into the state in place on the caller's stream: no read-back, no memset (the caller zeroes a new state).
+ *                 Integer sums: exact, and two states merge by addition.  Two launches, no atomics.
+ *     workspace   one int32 state per 256 rows, rounded up to 8 bytes.
+ *   Inception Score  logits[n][ld]: classes = 2 .. 4096; order: int32[n] row numbers (position p reads row order[p]; every
+ *                 entry in 0 .. n - 1, not checked) or null: the given order.  Split k = positions [k n / splits,
+ *                 (k + 1) n / splits).  kl_out[splits]: mean over the split's rows of KL(p_row || p_mean), in float64; the
+ *                 score is exp of it.  row_h: null, or double[n]: sum_c p_c log p_c of the row at each position.  Three
+ *                 launches (a wave per row; a thread per class over chunks of 256 positions; a block per split), no atomics,
+ *                 fixed summation orders: the same input gives the same bits, whatever chunks_per_block (how many chunks one
+ *                 block of the second launch walks; 0: the library chooses, else 1 .. 64).
+ *     workspace   3 n + splits x slots x (classes + 1) doubles, slots = ceil(ceil(n / splits) / 256).
+ * RCDM_EINVAL: a null descriptor or pointer (thresholds, order and row_h may be null); n < 1, splits < 1, splits > n, ld below
+ * classes, an unknown dtype, chunks_per_block outside 0 .. 64, flags != 0, a misaligned pointer (logits at their element size,
+ * thresholds and order at 4, state, kl_out, row_h and workspace at 8).  RCDM_ESHAPE: classes outside the range, n > 2^30,
+ * splits > 65535.  RCDM_EWORKSPACE: workspace null or short.  All checked before anything is launched; the *_workspace_bytes
+ * and rcdm_label_state_len give 0 for what would be refused.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t ld_logits;               /* elements between rows of logits, >= classes */
+  int64_t ld_labels;               /* bytes between rows of labels, >= classes */
+  int32_t n, classes;
+  int32_t dtype;                   /* RCDM_FSTATS_*: the logits */
+  uint32_t flags;                  /* 0 */
+} rcdm_label_desc;
+typedef struct {
+  int64_t ld;                      /* elements between rows of logits, >= classes */
+  int32_t n, classes, splits;
+  int32_t dtype;                   /* RCDM_FSTATS_* */
+  int32_t chunks_per_block;        /* 0: the library chooses */
+  uint32_t flags;                  /* 0 */
+} rcdm_isc_desc;
+int64_t rcdm_label_state_len(int32_t classes);
+size_t rcdm_label_counts_workspace_bytes(const rcdm_label_desc* d);
+int rcdm_label_counts(const rcdm_label_desc* d, const void* logits, const uint8_t* labels, const float* thresholds, int64_t* state,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t rcdm_inception_score_workspace_bytes(const rcdm_isc_desc* d);
+int rcdm_inception_score(const rcdm_isc_desc* d, const void* logits, const int32_t* order, double* kl_out, double* row_h,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
  * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
  * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the

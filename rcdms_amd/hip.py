@@ -163,6 +163,16 @@ class PrdcDesc(C.Structure):
                 ("dtype", C.c_int32), ("col_chunks", C.c_int32), ("flags", C.c_uint32)]
 
 
+class LabelDesc(C.Structure):
+    _fields_ = [("ld_logits", C.c_int64), ("ld_labels", C.c_int64), ("n", C.c_int32), ("classes", C.c_int32), ("dtype", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
+class IscDesc(C.Structure):
+    _fields_ = [("ld", C.c_int64), ("n", C.c_int32), ("classes", C.c_int32), ("splits", C.c_int32), ("dtype", C.c_int32),
+                ("chunks_per_block", C.c_int32), ("flags", C.c_uint32)]
+
+
 class TokAdded(C.Structure):
     _fields_ = [("text", C.c_uint8 * 32), ("len", C.c_int32), ("id", C.c_int32), ("special", C.c_int32), ("reserved", C.c_int32)]
 
@@ -178,6 +188,8 @@ FSTATS_F32, FSTATS_F16 = 0, 1                            # FStatsDesc.dtype
 FRECHET_MAX_DIM = 4096
 KID_MAX_M, KID_MAX_SUBSETS, KID_MAX_DEGREE = 65536, 65535, 8   # kid::MAX_M, MAX_SUBSETS, MAX_DEGREE (d: FRECHET_MAX_DIM)
 PRDC_MAX_K, PRDC_MAX_N, PRDC_MAX_CHUNKS = 16, 65536, 1024      # prdc::MAX_K, MAX_N, MAX_CHUNKS (d: FRECHET_MAX_DIM)
+SCORES_MAX_LABEL_CLASSES, SCORES_MIN_CLASSES, SCORES_MAX_CLASSES = 64, 2, 4096    # sc::MAX_LABEL_CLASSES, MIN_CLASSES, MAX_CLASSES
+SCORES_MAX_SPLITS, SCORES_MAX_N, SCORES_MAX_CHUNKS_PER_BLOCK = 65535, 1 << 30, 64  # sc::MAX_SPLITS, MAX_N, MAX_CHUNKS_PER_BLOCK
 CHOLESKY_NB = 16                                          # fr::CHOL_NB, the panel width CholeskyDesc.nb = 0 stands for
 SSIM_UNIFORM7, SSIM_GAUSS11 = 0, 1                        # MetricsDesc.window
 PNG_BLOCK, PNG_SLOT, PNG_ADAPTIVE = 32768, 41728, -1      # RCDM_PNG_*
@@ -294,6 +306,11 @@ SYMBOLS = {
     "rcdm_knn_radii2": (C.c_int, [C.POINTER(KnnDesc), _P, _P, _P, _SZ, _P]),
     "rcdm_prdc_counts_workspace_bytes": (_SZ, [C.POINTER(PrdcDesc)]),
     "rcdm_prdc_counts": (C.c_int, [C.POINTER(PrdcDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_label_state_len": (C.c_int64, [_I]),
+    "rcdm_label_counts_workspace_bytes": (_SZ, [C.POINTER(LabelDesc)]),
+    "rcdm_label_counts": (C.c_int, [C.POINTER(LabelDesc), _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_inception_score_workspace_bytes": (_SZ, [C.POINTER(IscDesc)]),
+    "rcdm_inception_score": (C.c_int, [C.POINTER(IscDesc), _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -770,6 +787,28 @@ def prdc_counts_workspace_bytes(desc):
 def prdc_counts(desc, x, y, rx2, ry2, out, fake_count, real_hit, real_min2, workspace, workspace_bytes, stream=None):
     _check(load().rcdm_prdc_counts(C.byref(desc), x, y, rx2, ry2, out, fake_count, real_hit, real_min2, workspace, workspace_bytes,
                                    _st(stream)), "rcdm_prdc_counts")
+
+
+def label_state_len(classes):
+    return int(load().rcdm_label_state_len(classes))
+
+
+def label_counts_workspace_bytes(desc):
+    return int(load().rcdm_label_counts_workspace_bytes(C.byref(desc)))
+
+
+def label_counts(desc, logits, labels, thresholds, state, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_label_counts(C.byref(desc), logits, labels, thresholds, state, workspace, workspace_bytes, _st(stream)),
+           "rcdm_label_counts")
+
+
+def inception_score_workspace_bytes(desc):
+    return int(load().rcdm_inception_score_workspace_bytes(C.byref(desc)))
+
+
+def inception_score(desc, logits, order, kl_out, row_h, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_inception_score(C.byref(desc), logits, order, kl_out, row_h, workspace, workspace_bytes, _st(stream)),
+           "rcdm_inception_score")
 
 
 def frame_metrics_workspace_bytes(desc):

@@ -12,7 +12,15 @@ pool), evaluated with the kernels of csrc/conv2d.hip:
 The weights are the caller's: a state dict with torchvision's keys.  There is no concat copy and no CPU path; a launch plan
 (buffers + descriptors, one stream, program order) is built once per chunk size N (the network runs at 299 x 299 whatever the frames' H x W: only the bilinear descriptor,
 made per call, sees them — so every (N, H, W) finds its plan, and two frame sizes share one) and kept in a small LRU, and a large N runs in
-chunks of `batch` frames.  Restated from the published architecture and tested against tests/inception_oracle.py."""
+chunks of `batch` frames.  Restated from the published architecture and tested against tests/inception_oracle.py.
+
+Classifier input (preprocess="pillow"): the character classifiers of the StoryGAN -> DUCO -> StoryDALL-E -> ARLDM lineage are
+torchvision Inception-v3 networks fed `Resize((299, 299))` on a PIL image — Pillow's antialiased 8-bit bilinear — then `ToTensor`
+and `Normalize(mean, std)`.  That is rcdm_image_resample in RCDM_IMAGE_F16_ROWS mode (image.Resampler.to_rows: Pillow's bytes
+bit for bit, then (u8 / 255 - mean) / std rounded to f16) writing the plan's input rows; the ImageNet constants are the default.
+torchvision's `transform_input=True` is a per-channel affine map x' = x std / 0.5 + (mean - 0.5) / 0.5 of the normalised pixel:
+it folds into the constants, and with the ImageNet mean / std the folded ones are mean = std = (0.5, 0.5, 0.5) exactly.  No
+classifier weights ship with the project; the preprocessing is reproduced from the published transforms."""
 from collections import OrderedDict
 
 import torch
@@ -23,6 +31,9 @@ from .metrics import _frames, _view
 EPS = 1e-3
 SIDE = 299
 VARIANTS = ("fid", "torchvision")
+PREPROCESS = ("fid", "pillow")
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+TRANSFORM_INPUT_MEAN = TRANSFORM_INPUT_STD = (0.5, 0.5, 0.5)      # ImageNet constants with transform_input=True folded in
 
 
 def _pair(v):
@@ -268,11 +279,23 @@ class InceptionV3Features:
     """state_dict: torchvision's Inception3 keys (`<Block>.<branch>.conv.weight`, `.bn.{weight,bias,running_mean,running_var}`,
     `fc.weight`, `fc.bias`; AuxLogits.* and num_batches_tracked ignored); num_classes is fc.weight's row count.
     variant: "fid" (pytorch-fid's FID Inception) or "torchvision".  batch: frames per chunk of a large call.
-    blocks: only for tests — build just these Mixed_* blocks (run_block), no stem, no fc."""
+    blocks: only for tests — build just these Mixed_* blocks (run_block), no stem, no fc.
+    preprocess: "fid" (torch's bilinear without antialias to 299 x 299, 2 x - 1: the FID input) or "pillow" (Pillow's 8-bit
+    bilinear to 299 x 299, then (u8 / 255 - mean) / std: a torchvision classifier's input; mean, std default to ImageNet's)."""
 
-    def __init__(self, state_dict, variant="fid", device="cuda", batch=50, plans=4, blocks=None):
+    def __init__(self, state_dict, variant="fid", device="cuda", batch=50, plans=4, blocks=None, *, preprocess="fid", mean=None,
+                 std=None):
         if variant not in VARIANTS:
             raise ValueError(f"variant {variant!r}: one of {VARIANTS}")
+        if preprocess not in PREPROCESS:
+            raise ValueError(f"preprocess {preprocess!r}: one of {PREPROCESS}")
+        if preprocess == "fid" and (mean is not None or std is not None):
+            raise ValueError("mean and std belong to preprocess='pillow': the FID input is 2 x - 1")
+        self.preprocess = preprocess
+        self.mean = tuple(float(v) for v in (IMAGENET_MEAN if mean is None else mean))
+        self.std = tuple(float(v) for v in (IMAGENET_STD if std is None else std))
+        if len(self.mean) != 3 or len(self.std) != 3 or not all(v > 0.0 for v in self.std) or any(v != v for v in self.mean):
+            raise ValueError(f"mean and std are three numbers each, std above 0, got {mean} and {std}")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise hip.RcdmError("InceptionV3Features runs on the HIP path only: there is no CPU path here")
@@ -330,14 +353,42 @@ class InceptionV3Features:
         p.last = x
         return p
 
-    def _forward_chunk(self, frames, feats, logits):
-        """frames (n, H, W, 3) uint8 view (any pitch, one stride), n <= batch; feats fp32 (n, 2048), logits fp32 (n, classes) or None."""
+    def _input_rows(self, frames, dst_ptr):
+        """frames (n, H, W, 3) uint8 view -> n * 299 * 299 f16 rows of 8 channels at dst_ptr: one launch."""
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-        plan = self._plan(("net", n), lambda: self._build_net(n))
+        if self.preprocess == "pillow":
+            from . import image
+            image.resampler(H, W, SIDE, SIDE, "bilinear", None, self.device).to_rows(frames, self.mean, self.std, dst_ptr, 8, 8)
+            return
         pitch = frames.stride(1) if H > 1 else 3 * W
         stride = frames.stride(0) if n > 1 else 0
         d = hip.BilinearDesc(pitch, stride, n, 3, H, W, SIDE, SIDE, 0, 8, 8, (2.0, 2.0, 2.0), (-1.0, -1.0, -1.0))
-        hip.image_bilinear_rows(d, frames.data_ptr(), plan.x0.ptr)
+        hip.image_bilinear_rows(d, frames.data_ptr(), dst_ptr)
+
+    def _checked(self, frames):
+        frames = _frames("frames", frames)
+        if not frames.is_cuda:
+            raise hip.RcdmError("InceptionV3Features runs on the HIP path only: frames must be a device tensor (there is no CPU path here)")
+        if frames.device != self.device:
+            raise ValueError(f"frames are on {frames.device}, the extractor on {self.device}")
+        return _view(frames)
+
+    @torch.no_grad()
+    def preprocessed_rows(self, frames):
+        """The network's input for these frames, as `preprocess` makes it: f16 (N, 299, 299, 8), channels 3 .. 7 zero.  A buffer
+        of its own (no plan is built or touched); for tests and for comparing against a classifier's own transforms."""
+        v = self._checked(frames)
+        rows = torch.empty(v.shape[0] * SIDE * SIDE, 8, dtype=torch.float16, device=self.device)
+        with torch.cuda.device(self.device):
+            for i in range(0, v.shape[0], self.batch):
+                self._input_rows(v[i:i + self.batch], rows[i * SIDE * SIDE:].data_ptr())
+        return rows.view(v.shape[0], SIDE, SIDE, 8)
+
+    def _forward_chunk(self, frames, feats, logits):
+        """frames (n, H, W, 3) uint8 view (any pitch, one stride), n <= batch; feats fp32 (n, 2048), logits fp32 (n, classes) or None."""
+        n = frames.shape[0]
+        plan = self._plan(("net", n), lambda: self._build_net(n))
+        self._input_rows(frames, plan.x0.ptr)
         plan.run()
         last = plan.last
         hip.global_avgpool(n, last.h * last.w, last.c, last.ptr, last.ld, feats.data_ptr(), feats.stride(0))

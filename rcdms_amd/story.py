@@ -155,11 +155,14 @@ class StoryRunner:
     tower with projection (`.image_embeds`, `.last_hidden_state`); clip_processor: frames -> pixel values (default
     rcdms_amd.image.ClipImageProcessor at the encoder's image size); frame_transform: frames -> stage-2 source frames in
     [-1, 1] (default rcdms_amd.image.FrameTransform at the UNet's sample size); inception: an
-    rcdms_amd.inception.InceptionV3Features (uint8 frames -> (n, 2048) fp32), the extractor of feature_source="inception"."""
+    rcdms_amd.inception.InceptionV3Features (uint8 frames -> (n, 2048) fp32), the extractor of feature_source="inception";
+    classifier: a second InceptionV3Features, the character classifier whose logits label_counts scores (other weights than the
+    FID network's, usually preprocess="pillow")."""
 
-    def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None, inception=None):
+    def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None, inception=None,
+                 classifier=None):
         self.prior_pipe, self.stage2_pipe, self.image_encoder = prior_pipe, stage2_pipe, image_encoder
-        self.inception = inception
+        self.inception, self.classifier = inception, classifier
         if clip_processor is None:
             from .image import ClipImageProcessor
             size = int(image_encoder.config.image_size)
@@ -210,7 +213,7 @@ class StoryRunner:
                  guidance_scale=7.5, prior_guidance_scale=4.0, generator=None, prior_generator=None, output_type="tensor",
                  save_dir=None, indices=None, stage2=None, fix_context_order=False, guidance_rescale=0.0, eta=0.0, metrics=(),
                  stage2_autoreg=False, frames_dir=None, grid_dir=None, feature_stats=None, feature_banks=None,
-                 feature_source="clip"):
+                 feature_source="clip", labels=None, label_counts=None, label_frames=None, logit_bank=None):
         """frames: uint8 (S, 5, Hs, Ws, 3) RGB, host or device; texts: S lists of five captions (lower-cased here, as the
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
@@ -231,6 +234,15 @@ class StoryRunner:
         frames), `reference` inception(the five given uint8 frames of every story), 2048 wide: the inputs of an Inception FID /
         KID.  The CLIP forward over the generated frames then runs only when "clip_i" is asked for as well.  Without an extractor,
         or with an output type that leaves no uint8 frames, "inception" is a ValueError before anything is launched.
+        label_counts: an rcdms_amd.scores.LabelCounts: the runner's `classifier` runs on the generated uint8 frames and its logits
+        are scored against `labels`, uint8 (S, 5, C) character labels (non-zero: present), C the classifier's num_classes and
+        the counts' — the sufficient statistics of Char-F1 / Frm-Acc over as many calls as the caller likes, no read-back.
+        label_frames: the frame indices scored, default all five (continuation papers score (1, 2, 3, 4): frame 0 is given).
+        logit_bank: an rcdms_amd.kid.FeatureBank of width inception.num_classes that keeps the logits of the generated frames
+        (for rcdms_amd.scores.inception_score), from the one forward feature_source="inception" runs on them — required —, which
+        then also returns its logits: no second forward.  Both need a stage-2 run that leaves uint8 frames; a missing
+        extractor, missing labels or a width mismatch is a ValueError before anything is launched.  None: nothing more is
+        launched.
         stage2_autoreg: the stage-2 driver's --autoreg loop (stage2…:304-362) for the S stories, independent of `autoreg`
         (stage 1's loop): five stage-2 calls at batch S, pass i keeping frame i of every story —
           pass 0: the call of stage2_autoreg=False (given frame 0 seen, image_embeds_1 its hidden state, proj_embeds_0
@@ -277,6 +289,20 @@ class StoryRunner:
                 raise ValueError(f"{name} collect the embeddings of the frames stage 2 generates: this call runs no stage 2")
             if output_type != "uint8" and not stage2_autoreg:
                 raise ValueError(f"{name} are taken from uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
+        for name, given in (("label_counts", label_counts), ("logit_bank", logit_bank)):
+            if given is None:
+                continue
+            if not stage2:
+                raise ValueError(f"{name} takes the logits of the frames stage 2 generates: this call runs no stage 2")
+            if output_type != "uint8" and not stage2_autoreg:
+                raise ValueError(f"{name} is filled from uint8 frames: pass output_type=\"uint8\", not {output_type!r}")
+        labels, label_frames = self._check_labels(frames, labels, label_counts, label_frames)
+        if logit_bank is not None:
+            if self.inception is None or feature_source != "inception":
+                raise ValueError('logit_bank keeps the logits of the forward feature_source="inception" runs: build the runner with '
+                                 'inception=InceptionV3Features(...) and pass feature_source="inception"')
+            if logit_bank.d != self.inception.num_classes:
+                raise ValueError(f"logit_bank is {logit_bank.d} wide, the extractor has {self.inception.num_classes} classes")
         if metrics and not stage2:
             raise ValueError(f"metrics {metrics} compare the frames stage 2 generates with their targets: this call runs no stage 2")
         if stage2_autoreg and not stage2:
@@ -358,11 +384,33 @@ class StoryRunner:
                 write_story_pngs(frames_dir, grid_dir, indices, frames_u8,
                                  self.target_frames(frames) if grid_dir is not None else None, files)
         figures = {}
-        if metrics or feature_stats is not None or feature_banks is not None:
+        if metrics or feature_stats is not None or feature_banks is not None or label_counts is not None or logit_bank is not None:
             figures = self.story_metrics(frames_u8 if stage2_autoreg else videos, frames, target, metrics, feature_stats,
-                                         feature_banks, feature_source)
+                                         feature_banks, feature_source, labels, label_counts, label_frames, logit_bank)
         return StoryResult(videos=videos, image_embeds=embeds, target_embeds=target, cosine=cosine, **figures,
                            frames_u8=frames_u8 if stage2_autoreg else None)
+
+    def _check_labels(self, frames, labels, label_counts, label_frames):
+        """The label arguments of a call, checked on the host -> (labels as a uint8 tensor or None, label_frames as a list or None)."""
+        if label_counts is None:
+            if labels is not None or label_frames is not None:
+                raise ValueError("labels / label_frames are scored into label_counts: pass a LabelCounts")
+            return None, None
+        if self.classifier is None:
+            raise ValueError("label_counts needs a classifier: build the runner with classifier=InceptionV3Features(...)")
+        if labels is None:
+            raise ValueError("label_counts scores the classifier's logits against `labels`: uint8 (S, 5, C)")
+        labels = torch.as_tensor(labels)
+        C = self.classifier.num_classes
+        if labels.dtype != torch.uint8 or labels.dim() != 3 or tuple(labels.shape[:2]) != (np.shape(frames)[0], FRAMES):
+            raise ValueError(f"labels are uint8 (S, {FRAMES}, C) for the S stories of `frames`, got {labels.dtype} {tuple(labels.shape)}")
+        if labels.shape[2] != C or label_counts.num_classes != C:
+            raise ValueError(f"the classifier has {C} classes, labels {labels.shape[2]} and label_counts {label_counts.num_classes}")
+        if label_frames is not None:
+            label_frames = [int(i) for i in label_frames]
+            if not label_frames or len(set(label_frames)) != len(label_frames) or not all(0 <= i < FRAMES for i in label_frames):
+                raise ValueError(f"label_frames are distinct frame indices in 0..{FRAMES - 1}, got {label_frames}")
+        return labels, label_frames
 
     def _stage2_bytes(self, source, label, img1, proj0, output_type, kw):
         """One stage-2 call whose frames are also wanted as bytes -> (videos, device uint8 (S, 5, H, W, 3)).  "tensor": the
@@ -406,11 +454,13 @@ class StoryRunner:
         r = resampler(flat.shape[1], flat.shape[2], ft.height, ft.width, ft.resample, None, flat.device)
         return r.to_uint8(flat, ft.flip_channels).view(S, FRAMES, ft.height, ft.width, 3)
 
-    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None, feature_banks=None, feature_source="clip"):
+    def story_metrics(self, videos, frames, target_embeds, metrics, feature_stats=None, feature_banks=None, feature_source="clip",
+                      labels=None, label_counts=None, label_frames=None, logit_bank=None):
         """videos: uint8 (S, 5, H, W, 3) as stage 2 returns them; frames: the given uint8 (S, 5, Hs, Ws, 3) on the device.
         -> {name: (S, 5) tensor} for the names in `metrics`.  feature_stats: (generated, reference) FeatureStats that take the
         embeddings of `videos` and target_embeds; feature_banks: (generated, reference) FeatureBanks that keep the same rows.
-        feature_source="inception": both pairs receive the runner's Inception features of `videos` and of `frames` instead."""
+        feature_source="inception": both pairs receive the runner's Inception features of `videos` and of `frames` instead.
+        label_counts / labels / label_frames / logit_bank: as in __call__ (checked there)."""
         from .metrics import frame_metrics
         if feature_source not in FEATURE_SOURCES:
             raise ValueError(f"feature_source {feature_source!r}: one of {FEATURE_SOURCES}")
@@ -430,7 +480,14 @@ class StoryRunner:
                 out["psnr"] = fm.psnr.view(S, FRAMES)
         if "clip_i" in metrics or (wants_rows and not inception):
             e = self.image_encoder(self._pixels(videos.reshape(S * FRAMES, *videos.shape[2:]))).image_embeds
-        if wants_rows and inception:
+        if logit_bank is not None:
+            if not inception or videos.dtype != torch.uint8:
+                raise ValueError('logit_bank is filled by the forward of feature_source="inception" over uint8 frames')
+            gen_rows, gen_logits = self.inception(videos.reshape(S * FRAMES, *videos.shape[2:]), return_logits=True)
+            logit_bank.append(gen_logits)
+            if wants_rows:
+                ref_rows = self.inception(frames.reshape(S * FRAMES, *frames.shape[2:]))
+        elif wants_rows and inception:
             gen_rows = self.inception(videos.reshape(S * FRAMES, *videos.shape[2:]))
             ref_rows = self.inception(frames.reshape(S * FRAMES, *frames.shape[2:]))
         elif wants_rows:
@@ -443,6 +500,14 @@ class StoryRunner:
             generated, reference = feature_banks
             generated.append(gen_rows)
             reference.append(ref_rows)
+        if label_counts is not None:
+            if self.classifier is None or labels is None or videos.dtype != torch.uint8:
+                raise ValueError("label_counts needs the runner's classifier, `labels` and uint8 frames")
+            _, logits = self.classifier(videos.reshape(S * FRAMES, *videos.shape[2:]), return_logits=True)
+            logits, lab = logits.view(S, FRAMES, -1), torch.as_tensor(labels).to(logits.device)
+            if label_frames is not None:
+                logits, lab = logits[:, list(label_frames)], lab[:, list(label_frames)]
+            label_counts.update(logits, lab)
         if "clip_i" in metrics:
             out["clip_i"] = torch.nn.functional.cosine_similarity(e.reshape(S, FRAMES, -1).float(), target_embeds.float(), dim=-1)
         return out
