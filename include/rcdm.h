@@ -106,14 +106,24 @@ int rcdm_gemm_ln(const rcdm_gemm_desc* d, const rcdm_ln_fuse* ln, const void* A,
  * pack time; for pos_encoder a per-frame row table b'_f = b' + W pe_f passed as `rowvec`):
  *     LayerNorm(x) W^T + b  =  rstd (x W'^T) - (rstd mean) S + b',      S[n] = sum_c f16(W'[n][c]).
  *   PRODUCER (the GEMM that writes the rows x, e.g. to_out + residual or proj_in): stat_out[slot][m] (float2 each, slot-major:
- *     a consumer's lanes read consecutive rows of one slot) = (sum, sum of squares) of the f16 values it stores to row m,
- *     one slot per column tile of its launch.  stat_parts
+ *     a consumer's lanes read consecutive rows of one slot) = (sum_t, M2_t) of the n_t f16 values it stores to row m in
+ *     column tile t, one slot per column tile of its launch: the tile's sum and its CENTRED sum of squares, formed as
+ *     shifted sums about the row's first stored value k of the tile (d = x - k is exact in fp32):
+ *         sum_t = sum(d) + n_t k,    M2_t = max(0, sum(d^2) - sum(d)^2 / n_t).
+ *     Slots stay independent, so two producers may fill one buffer.  stat_parts
  *     must equal rcdm_gemm_stat_parts(d) (the column-tile count of the tile shape a statistics-producing launch of this
  *     shape uses; RCDM_ESHAPE otherwise).  Plain / bias / row-vector / residual epilogues, no GEGLU, no split-K.
  *   CONSUMER (A = the RAW rows x, W = f16(W'), bias = b', colsum = S in the packed column order of W): stat_in / parts_in
- *     = the producer's partials of the A rows, C = the LayerNorm width (= K), eps.  Its epilogue forms (rstd, mean rstd)
- *     per row from the partials (var = E[x^2] - mean^2 in fp32) and applies the identity before bias / row vector /
- *     GELU / GEGLU / residual.  Every epilogue form, no split-K; parts_in <= 20.
+ *     = the producer's partials of the A rows, C = the LayerNorm width, eps.  Its epilogue merges the slots about the first
+ *     tile's mean K = sum_0 / n_0 (a_t = sum_t / n_t):
+ *         U = sum_t n_t (a_t - K),   Q = sum_t [M2_t + n_t (a_t - K)^2],   mean = K + U / C,   var = (Q - U^2 / C) / C,
+ *     so nothing of the size of mean^2 is ever formed: on rows with |mean| / sigma up to 256 rstd is within 1.5e-5 (relative,
+ *     the finest threshold of the probe) and the mean within 3.2e-5 sigma of float64, a constant row gives var = 0 up to
+ *     the rounding of its mean (measured on an MI355X, tests/test_hip_ln_cond.py; E[x^2] - mean^2, which this replaces,
+ *     was off by up to 1.6e-2 there).  n_t is
+ *     the producer's tile width (the last tile: what is left of C), which (C, parts_in) determines: parts_in = 1, or
+ *     ceil(C / 64), ceil(C / 128), ceil(C / 256); any other count is RCDM_ESHAPE.  (rstd, mean rstd), bias and the row
+ *     vector are applied to the fp32 accumulators, before GELU / GEGLU / residual and before the one rounding to f16.  Every epilogue form, no split-K; parts_in <= 20.
  *   One call may be both.  Both sides NULL = rcdm_gemm. */
 typedef struct {
   float* stat_out;            /* producer: slot-major [stat_parts][stat_out_rows][2] fp32, or NULL */

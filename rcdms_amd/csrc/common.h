@@ -170,13 +170,30 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-// Deferred LayerNorm, consumer side: TPR consecutive lanes (1, 2 or 4) share a row and split its <= MAXP partial
-// (sum, sum of squares) slots; finish() gives (rstd, mean * rstd) of the row in every lane of the group.
+// the value of the FIRST lane of every group of LPR consecutive lanes (8 or 16), in every lane of the group: quad broadcast, then
+// row_shr 4 into the odd quads and row_shr 8 into the upper half of the 16-lane row (bank masks: the other lanes keep theirs)
+template <int LPR>
+__device__ __forceinline__ float group_first(float v) {
+  static_assert(LPR == 8 || LPR == 16, "groups inside one 16-lane row");
+  int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xF, 0xF, true);   // quad_perm [0,0,0,0]
+  x = __builtin_amdgcn_update_dpp(x, x, 0x114, 0xF, 0xA, false);                      // row_shr:4 -> quads 1 and 3
+  if constexpr (LPR == 16) x = __builtin_amdgcn_update_dpp(x, x, 0x118, 0xF, 0xC, false);   // row_shr:8 -> quads 2 and 3
+  return __int_as_float(x);
+}
+
+// Deferred LayerNorm, consumer side.  The column counts of the producer's slots: every slot but the last covers `bn` columns
+// (the producer's tile width), the last one `last` (C - (parts - 1) bn: ragged when C is no multiple of bn; one slot: both are C)
+struct LnxGeo {
+  float bn, inv_bn, last, inv_last;
+};
+// TPR consecutive lanes (1, 2 or 4) share a row and split its <= MAXP partial slots (sum_t, M2_t) — the column tile's sum and
+// its centred sum of squares (igemm_args.h) —; finish() merges them about the pivot K = the first tile's mean and gives
+// (rstd, mean * rstd) of the row in every lane of the group.
 template <int TPR, int MAXP>
 struct LnxRow {
   static constexpr int NL = (MAXP + TPR - 1) / TPR;
   f32x2 v[NL];
-  // layout: slot-major, stat[slot][ld rows] of (sum, sum of squares) — the lanes of a load instruction (consecutive rows of
+  // layout: slot-major, stat[slot][ld rows] of (sum_t, M2_t) — the lanes of a load instruction (consecutive rows of
   // one slot) read consecutive 8-byte pairs.  Loads go through a buffer descriptor of exactly parts * ld pairs: a slot past
   // `parts` (and a dead row, sent to offset 2^31) reads as zero in hardware, so there is neither a branch per element (which
   // hipcc turns into a wait per element) nor a clamp / select / 64-bit address per element — issuing the ten loads of the
@@ -193,38 +210,55 @@ struct LnxRow {
       off += stride;
     }
   }
-  __device__ __forceinline__ void finish(float invC, float eps, float& rstd, float& mr) const {
-    f32x2 s = v[0];
+  // Slot t covers n_t columns (LnxGeo) and has the mean a_t = sum_t / n_t.  In one pass over the slots, with K = a_0:
+  //   U = sum_t n_t (a_t - K),  Q = sum_t [M2_t + n_t (a_t - K)^2];   mean = K + U / C,  var = (Q - U^2 / C) / C.
+  // Every term is of the size of the row's spread, never of its offset squared.  A slot past the producer's count read zeros
+  // and has n_t = 0: it adds nothing.
+  __device__ __forceinline__ void finish(const LnxGeo& geo, int parts, float invC, float eps, int sub, float& rstd, float& mr) const {
+    float K = v[0].x * geo.inv_bn;   // (one slot: both widths are C)
+    if constexpr (TPR == 2) K = dpp_f32<0xA0>(K);   // quad_perm [0,0,2,2]: the group's first lane holds slot 0
+    if constexpr (TPR == 4) K = dpp_f32<0x00>(K);   // quad_perm [0,0,0,0]
+    float U = 0.f, Q = 0.f;
+    int t = sub - (parts - 1);   // slot index minus the last slot's
+    // (opaque: the selects below depend on nothing a persistent block's tile loop changes, and hipcc would form all 2 NL lane
+    // masks once in front of that loop and keep them in SGPR pairs it does not have)
+    asm volatile("" : "+v"(t));
 #pragma unroll
-    for (int j = 1; j < NL; ++j) s += v[j];
+    for (int j = 0; j < NL; ++j) {
+      const float n = t < 0 ? geo.bn : t == 0 ? geo.last : 0.f;
+      const float dlt = __builtin_fmaf(v[j].x, t == 0 ? geo.inv_last : geo.inv_bn, -K);
+      const float w = n * dlt;
+      U += w;
+      Q += __builtin_fmaf(w, dlt, v[j].y);
+      t += TPR;
+    }
     if constexpr (TPR >= 2) {
-      s.x += dpp_f32<0xB1>(s.x);
-      s.y += dpp_f32<0xB1>(s.y);
+      U += dpp_f32<0xB1>(U);
+      Q += dpp_f32<0xB1>(Q);
     }
     if constexpr (TPR >= 4) {
-      s.x += dpp_f32<0x4E>(s.x);
-      s.y += dpp_f32<0x4E>(s.y);
+      U += dpp_f32<0x4E>(U);
+      Q += dpp_f32<0x4E>(Q);
     }
-    const float mean = s.x * invC;
-    float var = __builtin_fmaf(-mean, mean, s.y * invC);
-    if (var < 0.f) var = 0.f;
+    const float um = U * invC;
+    const float mean = K + um;
+    const float var = fmaxf(__builtin_fmaf(-U, um, Q), 0.f) * invC;
     rstd = rsqrtf(var + eps);
     mr = mean * rstd;
   }
 };
 // (rstd, mean rstd) of row m with the load count sized to the slot count: <= 8 slots (C <= 1024 behind 128-wide producer
 // tiles) take the short form
-template <int TPR, int MAXP>
-__device__ __forceinline__ void lnx_row(const float* stat, int ld, int m, bool live, int parts, int sub, float invC, float eps,
-                                        float& rstd, float& mr) {
-  if (parts <= 8) {   // wave-uniform
+template <int TPR, int MAXP, class G>
+__device__ __forceinline__ void lnx_row(const G& g, const LnxGeo& geo, int m, bool live, int sub, float& rstd, float& mr) {
+  if (g.lnx_parts <= 8) {   // wave-uniform
     LnxRow<TPR, 8> r;
-    r.load(stat, ld, m, live, parts, sub);
-    r.finish(invC, eps, rstd, mr);
+    r.load(g.lnx_stat, g.lnx_ld, m, live, g.lnx_parts, sub);
+    r.finish(geo, g.lnx_parts, g.lnx_invC, g.lnx_eps, sub, rstd, mr);
   } else {
     LnxRow<TPR, MAXP> r;
-    r.load(stat, ld, m, live, parts, sub);
-    r.finish(invC, eps, rstd, mr);
+    r.load(g.lnx_stat, g.lnx_ld, m, live, g.lnx_parts, sub);
+    r.finish(geo, g.lnx_parts, g.lnx_invC, g.lnx_eps, sub, rstd, mr);
   }
 }
 

@@ -167,6 +167,30 @@ void igemm_dma_kernel(const IgemmArgs p) {
   static_assert(!LXC || LTPR == 1 || LTPR == 2 || LTPR == 4, "threads per row of the LayerNorm table");
   float* ltab = (float*)(smem + NSTAGE * (BM_ + BN_) * 128);
   float* lvS = ltab + 2 * BM_;   // [BN] S of the tile's channels
+  // the slots' column counts for the statistics of every tile after the first: read from LDS where they are needed (end of an
+  // epilogue), not kept in four more SGPRs for the whole kernel — the consumer kernels sit at the SGPR cap, and the scalars
+  // that no longer fit go to VGPR lanes and push vector registers into scratch
+  // ... followed by [BN] bias, [BN] the row vector of the first sample the tile meets and [BN] that of the second (zeros where
+  // the launch has none): everything the epilogue adds per column goes into the accumulators with the LayerNorm identity, so
+  // the staged half is the normalised projection itself and is rounded once, as the reference's fp16 Linear rounds it
+  float* lgeo = lvS + 4 * BN_;
+  static_assert((2 * BM_ + 4 * BN_) * 4 + sizeof(LnxGeo) <= kLnxTabBytes || !LXC, "the LayerNorm table behind the ring");
+  static_assert(!LXC || BN_ <= WM * WN * 64, "one thread per four table columns");
+  const bool lx_rvp = LXC && (p.epi & RCDM_EPI_ROWVEC) && !(p.epi & RCDM_EPI_GEGLU) && p.rows_per_sample >= BM_;
+  // this thread's four entries of the column tables of the tile at (m0, n0): S | bias | row vector | next sample's row vector
+  auto lx_cols = [&](int m0, int n0, int ts) __attribute__((always_inline)) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    const int grp = ts / (BN_ / 4), n = n0 + 4 * (ts % (BN_ / 4));
+    if (ts < BN_ && n < p.N) {
+      const int smp = lx_rvp ? m0 / p.rows_per_sample + (grp == 3) : 0;
+      if (grp == 0) v = *(const f32x4*)(p.lnx_S + n);
+      else if (grp == 1) { if (p.epi & RCDM_EPI_BIAS) v = *(const f32x4*)(p.bias + n); }
+      else if (lx_rvp && (grp == 2 || (smp * p.rows_per_sample < p.M && smp * p.rows_per_sample < m0 + BM_)))
+        v = *(const f32x4*)(p.rowvec + (size_t)smp * p.ldt + n);
+    }
+    return v;
+  };
+  if (LXC && threadIdx.x == 0) *(LnxGeo*)lgeo = p.lnx_geo;   // published by the barriers of the first tile's k-loop
   constexpr bool lnx_k = LXC;   // the (LX & 2) instantiation is only launched for consumers (p.lnx_stat != nullptr)
 
   const int ntiles = p.tilesM * p.tilesN;
@@ -261,7 +285,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
 #if !(RCDM_LNX_ABLATE & 1)
     lx_row0.load(p.lnx_stat, p.lnx_ld, lm, lm < p.M, p.lnx_parts, t % LTPR);
 #endif
-    if (t < BN_ / 4 && cn0 + 4 * t < p.N) lx_s4 = *(const f32x4*)(p.lnx_S + cn0 + 4 * t);
+    lx_s4 = lx_cols(cm0, cn0, t);
   }
 #ifdef RCDM_TRACE_LX
   if (p.trace) ts_a = __builtin_amdgcn_s_memtime() - ts0;
@@ -293,11 +317,14 @@ void igemm_dma_kernel(const IgemmArgs p) {
     const int lm = m0 + t / LTPR;
     float r_ = 1.f, m_ = 0.f;
 #if !(RCDM_LNX_ABLATE & 1)
-    lnx_row<LTPR, kLnxMaxParts>(p.lnx_stat, p.lnx_ld, lm, lm < p.M, p.lnx_parts, t % LTPR, p.lnx_invC, p.lnx_eps, r_, m_);
+    const f32x4 g4 = *(const f32x4*)lgeo;   // wave-uniform: back to scalars, four VGPRs would not fit either
+    auto sc = [](float v) __attribute__((always_inline)) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    lnx_row<LTPR, kLnxMaxParts>(p, LnxGeo{sc(g4[0]), sc(g4[1]), sc(g4[2]), sc(g4[3])}, lm, lm < p.M, t % LTPR, r_, m_);
 #endif
     lx_rs = f32x2{r_, m_};
-    lx_s4 = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (t < BN_ / 4 && n0 + 4 * t < p.N) lx_s4 = *(const f32x4*)(p.lnx_S + n0 + 4 * t);
+    int ts = t;   // (opaque: the address is formed here, not once in front of the tile loop and held in a VGPR pair)
+    asm volatile("" : "+v"(ts));
+    lx_s4 = lx_cols(m0, n0, ts);
   };
 #ifdef RCDM_TRACE_LX
   if (p.trace) ts_b = __builtin_amdgcn_s_memtime() - ts0;
@@ -305,7 +332,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
 #if !(RCDM_LNX_ABLATE & 1)
   if constexpr (LXC) {
     float r_, m_;
-    lx_row0.finish(p.lnx_invC, p.lnx_eps, r_, m_);
+    lx_row0.finish(p.lnx_geo, p.lnx_parts, p.lnx_invC, p.lnx_eps, t % LTPR, r_, m_);
     lx_rs = f32x2{r_, m_};
   }
 #endif
@@ -341,7 +368,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
     __builtin_amdgcn_s_barrier();
     if constexpr (LXC && !(RCDM_LNX_ABLATE & 128)) if (lx_now) {   // (after the barrier: the previous tile's epilogue is done reading the table)
       if (t % LTPR == 0) *(f32x2*)(ltab + 2 * (t / LTPR)) = lx_rs;
-      if (t < BN_ / 4) *(f32x4*)(lvS + 4 * t) = lx_s4;
+      if (t < BN_) *(f32x4*)(lvS + 4 * t) = lx_s4;
     }
     // 8-wave blocks put two waves on every SIMD, released by the same barrier: if both issued their DMA pieces first
     // (each piece stalls the issuing wave for ~100 cycles) the SIMD's matrix pipe would idle through both bursts.
@@ -385,17 +412,58 @@ void igemm_dma_kernel(const IgemmArgs p) {
       f32x2 rs[FM];
 #pragma unroll
       for (int j = 0; j < FM; ++j) rs[j] = *(const f32x2*)(ltab + 2 * ((wm * FM + j) * 32 + lr));
+      float sec[FM];   // 1: the row belongs to the second sample the tile meets
+      const int lx_switch = lx_rvp ? (cm0 / p.rows_per_sample + 1) * p.rows_per_sample : 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < FM; ++j) sec[j] = cm0 + (wm * FM + j) * 32 + lr >= lx_switch ? 1.f : 0.f;
 #pragma unroll
       for (int i = 0; i < FN; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x4 s4 = *(const f32x4*)(lvS + (wn * FN + i) * 32 + 8 * q + 4 * hi);   // S of this quad's 4 channels
+          const float* col = lvS + (wn * FN + i) * 32 + 8 * q + 4 * hi;   // this quad's 4 channels
+          const f32x4 s4 = *(const f32x4*)col;
+          f32x4 b4 = *(const f32x4*)(col + BN_);
+          if (lx_rvp) {   // (wave-uniform) rows of the second sample get its row vector: b + w (r1 - r0), w = 0 | 1
+            const f32x4 r0 = *(const f32x4*)(col + 2 * BN_), r1 = *(const f32x4*)(col + 3 * BN_);
+            b4 += r0;
+            const f32x4 d4 = r1 - r0;
 #pragma unroll
-          for (int j = 0; j < FM; ++j)
+            for (int j = 0; j < FM; ++j)
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-              acc[i][j][4 * q + e] = __builtin_fmaf(acc[i][j][4 * q + e], rs[j].x, -rs[j].y * s4[e]);
+              for (int e = 0; e < 4; ++e)
+                acc[i][j][4 * q + e] = __builtin_fmaf(acc[i][j][4 * q + e], rs[j].x,
+                                                      __builtin_fmaf(-rs[j].y, s4[e], __builtin_fmaf(sec[j], d4[e], b4[e])));
+          } else {
+#pragma unroll
+            for (int j = 0; j < FM; ++j)
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                acc[i][j][4 * q + e] = __builtin_fmaf(acc[i][j][4 * q + e], rs[j].x, __builtin_fmaf(-rs[j].y, s4[e], b4[e]));
+          }
         }
+    }
+    if constexpr (E16 && (LX & 2) != 0 && !(RCDM_LNX_ABLATE & 64)) {
+      // a row vector with fewer rows per sample than the tile has (a tile meets more than two samples: no column table holds
+      // them): added to the accumulators row by row, here, so that it too is in before the one rounding to f16
+      if ((p.epi & RCDM_EPI_ROWVEC) && !geglu && !lx_rvp) {   // (wave-uniform)
+#pragma unroll
+        for (int j = 0; j < FM; ++j) {
+          const int m = cm0 + (wm * FM + j) * 32 + lr;
+          const bool m_ok = m < p.M;
+          const float* rvr = p.rowvec + (size_t)((m_ok ? m : 0) / p.rows_per_sample) * p.ldt + cn0;
+#pragma unroll
+          for (int i = 0; i < FN; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int col = (wn * FN + i) * 32 + 8 * q + 4 * hi;
+              if (m_ok && cn0 + col < p.N) {
+                const f32x4 r4 = *(const f32x4*)(rvr + col);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += r4[e];
+              }
+            }
+        }
+      }
     }
     if constexpr (E16) {
       // ---- f16 staging (every launch without split-K): the accumulators are rounded to f16 (the reference's fp16
@@ -434,11 +502,12 @@ void igemm_dma_kernel(const IgemmArgs p) {
       float bA[8], bB[8], rvA[8], rvB[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) bA[e] = bB[e] = rvA[e] = rvB[e] = 0.f;
-      if ((p.epi & RCDM_EPI_BIAS) && pn_ok) {
+      // (a deferred-LayerNorm consumer has bias and the tile's row vectors in its accumulators already)
+      if ((p.epi & RCDM_EPI_BIAS) && pn_ok && !LXC) {
         load8(p.bias + pn, bA);
         if (geglu) load8(p.bias + pn + kGegluGroup, bB);
       }
-      if (rv_pair && pn_ok) {
+      if (rv_pair && pn_ok && !LXC) {
         load8(p.rowvec + (size_t)smp0 * p.ldt + pn, rvA);
         if (m_switch < p.M && m_switch < cm0 + BM_) load8(p.rowvec + (size_t)(smp0 + 1) * p.ldt + pn, rvB);
       }
@@ -532,9 +601,10 @@ void igemm_dma_kernel(const IgemmArgs p) {
 #pragma unroll
           for (int it0 = 0; it0 < P_ITEMS; it0 += RCH) {
             Pack16 hh[RCH];
-            float stv1[RCH], stv2[RCH];
+            // producer side of a deferred LayerNorm: this thread's 8 stored values as shifted sums about its own first one
+            float stk[RCH], stv1[RCH], stv2[RCH];
 #pragma unroll
-            for (int k = 0; k < RCH; ++k) stv1[k] = stv2[k] = 0.f;
+            for (int k = 0; k < RCH; ++k) stk[k] = stv1[k] = stv2[k] = 0.f;
 #pragma unroll
             for (int k = 0; k < RCH; ++k)
               if (it0 + k < P_ITEMS) {
@@ -546,8 +616,6 @@ void igemm_dma_kernel(const IgemmArgs p) {
               if (it0 + k < P_ITEMS) {
                 const int it = it0 + k;
                 const int m = mbase + pr0 + it * P_RPI;
-                float& st1 = stv1[k];          // producer side of a deferred LayerNorm: sums over this thread's 8 outputs
-                float& st2 = stv2[k];
                 if (m < p.M && pn_ok) {
                   const Pack16& rr = resv[WHOLE ? ps : 0][it];
                   Pack16 o;
@@ -561,7 +629,7 @@ void igemm_dma_kernel(const IgemmArgs p) {
                       const bool second = m >= m_switch;
 #pragma unroll
                       for (int e = 0; e < 8; ++e) v[e] += second ? rvB[e] : rvA[e];
-                    } else if (has_rv) {
+                    } else if (has_rv && !LXC) {   // (a deferred-LayerNorm consumer has it in its accumulators)
                       float rv[8];
                       load8(p.rowvec + (size_t)(m / p.rows_per_sample) * p.ldt + pn, rv);
 #pragma unroll
@@ -587,30 +655,47 @@ void igemm_dma_kernel(const IgemmArgs p) {
                   *(uint4*)(p.out + (size_t)m * p.ldc + pn) = o.u;
                   if (p.dup) *(uint4*)(p.out + (size_t)m * p.ldc + pn + p.dup) = o.u;
                   if (stat_on) {   // (v_dot2c_f32_f16 was tried for two elements per instruction: wrong sums on gfx950)
+                    stk[k] = (float)o.e[0];
+                    const float nk = -stk[k];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                      const float f = (float)o.e[e];
-                      st1 += f;
-                      st2 = __builtin_fmaf(f, f, st2);
+                    for (int e = 1; e < 8; ++e) {
+                      const float f = mix_f16_f32(o.v[e >> 1], e & 1, 1.f, nk);   // x - k in one instruction; exact: both are halfs
+                      stv1[k] += f;
+                      stv2[k] = __builtin_fmaf(f, f, stv2[k]);
                     }
                   }
                 }
               }
             if (stat_on) {
-              // wave-uniform; every lane of the P_TPR-lane row group takes part in the DPP sums.  The batch's 2 RCH reductions
-              // are independent chains the scheduler interleaves; one store per row and column tile
+              // the slot rule: igemm_args.h.  Wave-uniform; every lane of the P_TPR-lane row group takes part in the DPP sums.
+              // The row's pivot K is its first stored value of this column tile (the pc8 == 0 lane's own pivot); a lane moves its
+              // sums from its own pivot k to K with dk = k - K (exact): sum(f - K) = s + 8 dk, sum((f - K)^2) = q + dk (2 s + 8 dk)
+              // — nothing of the size of the row's offset is squared or added.  Lanes past N or M (nothing stored) add nothing.
+              // The batch's 3 RCH reductions are independent chains the scheduler interleaves; one store per row and column tile
+              const float stat_n = (float)min(BN_, p.N - cn0);
+              const float stat_inv_n = 1.f / stat_n;
+              float piv[RCH];
 #pragma unroll
               for (int k = 0; k < RCH; ++k) {
-                stv1[k] = group_sum<P_TPR>(stv1[k]);
-                stv2[k] = group_sum<P_TPR>(stv2[k]);
+                if constexpr (P_TPR <= 16) piv[k] = group_first<P_TPR>(stk[k]);
+                else piv[k] = group_sum<P_TPR>(pc8 == 0 ? stk[k] : 0.f);
+              }
+#pragma unroll
+              for (int k = 0; k < RCH; ++k) {
+                const bool on = pn_ok && mbase + pr0 + (it0 + k) * P_RPI < p.M;
+                const float dk = on ? stk[k] - piv[k] : 0.f, n8 = 8.f * dk;
+                stv2[k] = group_sum<P_TPR>(__builtin_fmaf(dk, 2.f * stv1[k] + n8, stv2[k]));
+                stv1[k] = group_sum<P_TPR>(stv1[k] + n8);
               }
               if (pc8 == 0) {
 #pragma unroll
                 for (int k = 0; k < RCH; ++k) {
                   const int m = mbase + pr0 + (it0 + k) * P_RPI;
                   if (it0 + k < P_ITEMS && m < p.M) {
-                    *(f32x2*)(p.stat_out + ((size_t)stat_tn * p.stat_ld + m) * 2) = f32x2{stv1[k], stv2[k]};
-                    if (dup_rows) *(f32x2*)(p.stat_out + ((size_t)stat_tn * p.stat_ld + m + dup_rows) * 2) = f32x2{stv1[k], stv2[k]};
+                    const f32x2 slot = {__builtin_fmaf(stat_n, piv[k], stv1[k]),
+                                        fmaxf(__builtin_fmaf(-stv1[k] * stat_inv_n, stv1[k], stv2[k]), 0.f)};
+                    *(f32x2*)(p.stat_out + ((size_t)stat_tn * p.stat_ld + m) * 2) = slot;
+                    if (dup_rows) *(f32x2*)(p.stat_out + ((size_t)stat_tn * p.stat_ld + m + dup_rows) * 2) = slot;
                   }
                 }
               }
@@ -1060,6 +1145,14 @@ int rcdm_gemm_lnx(const rcdm_gemm_desc* d, const rcdm_lnx* x, const void* A, con
     a.lnx_stat = x->stat_in; a.lnx_S = x->colsum; a.lnx_parts = x->parts_in; a.lnx_ld = x->stat_in_rows;
     if (a.lnx_ld < a.M) return RCDM_EINVAL;
     a.lnx_invC = 1.0f / (float)x->C; a.lnx_eps = x->eps;
+    // the producer's column-tile width, which the consumer's merge needs for the slots' column counts: with two slots or
+    // more ceil(C / 64), ceil(C / 128) and ceil(C / 256) differ, so the slot count names the width
+    int bn = x->parts_in == 1 ? x->C : 0;
+    for (int w = 64; w <= 256 && !bn; w *= 2)
+      if ((x->C + w - 1) / w == x->parts_in) bn = w;
+    if (!bn) return RCDM_ESHAPE;
+    const int last = x->C - (x->parts_in - 1) * bn;
+    a.lnx_geo = LnxGeo{(float)bn, 1.0f / (float)bn, (float)last, 1.0f / (float)last};
   }
   // the flags the launch carries, and a producer's slot count (the caller's, where an LDS-DMA tile has it: rcdm_gemm_lnx_parts_ok)
   int variant = 0;

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
   issue(0, 0);
   if (lx_on && t < BM) {
     float r_ = 1.f, m_ = 0.f;
-    lx_row0.finish(p.lnx_invC, p.lnx_eps, r_, m_);
+    lx_row0.finish(p.lnx_geo, p.lnx_parts, p.lnx_invC, p.lnx_eps, 0, r_, m_);
     lx_pre = f32x2{r_, m_};
   }
   for (int g = 0; g < nkl; ++g) {

@@ -320,7 +320,7 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
       f32x2 pre = {1.f, 0.f};
       if (t < BM) {
         float r_ = 1.f, m_ = 0.f;
-        lnx_row<1, kLnxMaxParts>(p.lnx_stat, p.lnx_ld, cm0 + t, cm0 + t < p.M, p.lnx_parts, 0, p.lnx_invC, p.lnx_eps, r_, m_);
+        lnx_row<1, kLnxMaxParts>(p, p.lnx_geo, cm0 + t, cm0 + t < p.M, 0, r_, m_);
         pre = f32x2{r_, m_};
       }
       float* tab = (float*)(smem + BM * (2 * BN + 16));

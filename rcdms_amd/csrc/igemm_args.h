@@ -36,8 +36,14 @@ struct IgemmArgs {
   f16* ln_out;
   int ln_ld, ln_rpf, ln_frames;
   float ln_eps;
-  // deferred LayerNorm (rcdm_gemm_lnx).  Producer side: stat_out[slot][m] = (sum, sum of squares) of the f16 values
-  // this launch stores to row m, one slot per column tile (stat_parts == tilesN).  Consumer side: the A rows are the RAW
+  // deferred LayerNorm (rcdm_gemm_lnx).  Producer side: stat_out[slot][m] = (sum_t, M2_t) of the n_t = min(BN, N - cn0) f16
+  // values this launch stores to row m in column tile t, one slot per column tile (stat_parts == tilesN), formed as shifted
+  // sums about the pivot k = the row's first stored value of the tile (d = f - k is exact in fp32):
+  //   sum_t = sum(d) + n_t k,   M2_t = max(0, sum(d^2) - sum(d)^2 / n_t)   (the tile's centred sum of squares).
+  // Consumer side (LnxRow::finish): mean = sum_t(sum_t) / C, M2 = sum_t[M2_t + (sum_t - n_t mean)^2 / n_t], var = M2 / C:
+  // nothing of the size of mean^2 is formed, so rows far from zero keep fp32's precision and a constant row has var = 0 up
+  // to the rounding of its mean.  n_t needs the producer's tile width (lnx_geo), which (C, lnx_parts) determines
+  // (rcdm_gemm_lnx).  The A rows are the RAW the A rows are the RAW
   // input x of a LayerNorm whose gamma is folded into W and whose beta into the bias, so LayerNorm(x) W^T =
   // rstd (x W'^T) - rstd mean S, S[n] = sum_c W'[n][c]: lnx_stat holds the producer's partials of the A rows, the epilogue
   // forms (rstd, mean rstd) per row and applies them before bias / row vector / GEGLU / residual.
@@ -47,6 +53,7 @@ struct IgemmArgs {
   const float* lnx_S;
   int lnx_parts, lnx_ld;
   float lnx_invC, lnx_eps;
+  LnxGeo lnx_geo;               // the slots' column counts: the producer's tile width and the last slot's (common.h)
   // nearest-2x upsample + conv3x3 as four 2x2 PHASE convolutions over the SOURCE grid (rcdm_conv3x3, upsample = 2; the
   // ping-pong kernel with TAPS = 4): output pixel (2y + a, 2x + b) sees only the 2x2 source pixels (y + a - 1 + r,
   // x + b - 1 + c), r, c in {0, 1}, each with the SUM of the 3x3 taps that land on it.  Virtual row m = phase * ph_rows +

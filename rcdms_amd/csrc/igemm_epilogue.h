@@ -131,7 +131,7 @@ __device__ __forceinline__ void tile_epilogue(const IgemmArgs& p, char* stg, f32
       const bool lx_rvp = lx_rv && p.rows_per_sample >= BM;     // both row vectors a tile can meet are in the tables
       const int lx_switch = lx_rvp ? (cm0 / p.rows_per_sample + 1) * p.rows_per_sample : 0x7fffffff;
       epi &= ~RCDM_EPI_BIAS;
-      if (lx_rvp) epi &= ~RCDM_EPI_ROWVEC;                      // (else the items add the row vector per row, as without lnx)
+      if (lx_rvp) epi &= ~RCDM_EPI_ROWVEC;                      // (else it is added row by row below)
       f32x2 rsj[FMW];
       bool secj[FMW];
 #pragma unroll
@@ -149,6 +149,26 @@ __device__ __forceinline__ void tile_epilogue(const IgemmArgs& p, char* stg, f32
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             acc[i][j][e] = __builtin_fmaf(acc[i][j][e], rsj[j].x, __builtin_fmaf(-rsj[j].y, s4[e], secj[j] ? c4[e] : b4[e]));
+      }
+      // a row vector with fewer rows per sample than the tile has (a tile meets more than two samples: the tables cannot hold
+      // them): added to the accumulators row by row, here, so that it too is in before the one rounding to f16
+      if (lx_rv && !lx_rvp && !(p.epi & RCDM_EPI_GEGLU)) {   // (wave-uniform)
+        epi &= ~RCDM_EPI_ROWVEC;
+#pragma unroll
+        for (int j = 0; j < FMW; ++j) {
+          const int m = cm0 + row0 + j * 16 + l15;
+          const bool m_ok = m < p.M;
+          const float* rvr = p.rowvec + (size_t)((m_ok ? m : 0) / p.rows_per_sample) * p.ldt + cn0;
+#pragma unroll
+          for (int i = 0; i < FNW; ++i) {
+            const int col = col0 + i * 16 + 4 * kg;
+            if (m_ok && cn0 + col < p.N) {
+              const f32x4 r4 = *(const f32x4*)(rvr + col);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[i][j][e] += r4[e];
+            }
+          }
+        }
       }
     }
 #pragma unroll

@@ -28,7 +28,7 @@ enum Family { kFamDma, kFamPP, kFam160 };   // igemm.hip (igemm_dma_kernel) / ig
 // what a variant has no kernel instantiation for
 enum : int { kNoStats = 1, kNoConsumer = 2, kNoConv = 4, kNoQuickGelu = 8 };
 
-constexpr int kLnxTabBytes = 3072;   // behind the ring of an LDS-DMA tile, deferred LayerNorm: [BM][2] floats (rstd, mean rstd) + [BN] floats S
+constexpr int kLnxTabBytes = 3328;   // behind the ring of an LDS-DMA tile, deferred LayerNorm: [BM][2] floats (rstd, mean rstd) + 4 [BN] floats (S, bias, two row vectors) + the slot widths
 struct VariantRow {
   int bm, bn, wm, wn, ring;   // tile, wave grid, LDS ring depth
   int blocks_per_cu;

@@ -1,10 +1,11 @@
-"""GPU parity tests of the deferred LayerNorm (rcdm_gemm_lnx): the GEMM that writes the token rows emits per-row partial
-(sum, sum of squares); the GEMM behind the LayerNorm takes the RAW rows with gamma / beta folded into its weights and
+"""GPU parity tests of the deferred LayerNorm (rcdm_gemm_lnx): the GEMM that writes the token rows emits per-row and column
+tile (sum, centred sum of squares); the GEMM behind the LayerNorm takes the RAW rows with gamma / beta folded into its weights and
 applies rstd (x W'^T) - rstd mean S + b' in its epilogue.  Reference (fp32 torch, the arithmetic of the reference's
 nn.LayerNorm + nn.Linear, attention.py:482-514 / motion_module.py:236-243 with PositionalEncoding :265-267):
     x = f16(A_p W_p^T + b_p + res);  y = epi(LayerNorm(x) (+ pe_f) W^T + b).
 Every tile shape (variants 1-10 as consumer — 8, the 256x256 ping-pong tile, refuses —, 1-5 and 10 as producer), plain / GEGLU / row-vector epilogues, ragged M, dup rows,
-rows whose mean is large against their spread (the cancellation case of E[x^2] - mean^2 and of the f16-staged x W'^T)."""
+rows whose mean is large against their spread (the cancellation case of the f16-staged x W'^T; the statistics' own conditioning
+is tests/test_hip_ln_cond.py's)."""
 import pytest
 import torch
 
@@ -41,25 +42,43 @@ def _producer(hip, Ap, Wp, bp, res, M, C, Kp, variant, dup=0):
 @pytest.mark.parametrize("pvariant", [1, 2, 3, 4, 5, 10])
 @pytest.mark.parametrize("M,C", [(640, 1280), (1000, 640), (300, 64)])
 def test_row_statistics(hiplib, M, C, pvariant):
-    """Producer side alone: the partial slots of a row sum to (sum, sum of squares) of the f16 values stored to that row."""
+    """Producer side alone: slot t of a row holds (sum_t, M2_t) of the f16 values stored to that row in column tile t — the
+    tile's sum and its centred sum of squares (the slot rule: igemm_args.h) —, on the draw of the other tests and on rows that
+    lie 100 sigma from zero."""
     from rcdms_amd import hip
-    g = torch.Generator().manual_seed(5 + M + C + pvariant)
-    Kp = 128
-    Ap = h16(torch.randn(M, Kp, generator=g))
-    Wp = h16(torch.randn(C, Kp, generator=g) * Kp ** -0.5)
-    bp = torch.randn(C, generator=g)
-    res = h16(torch.randn(M, C, generator=g) * 3 + 2.0)
-    x, stat, parts = _producer(hip, Ap, Wp, bp, res, M, C, Kp, pvariant)
-    xs = x.float().cpu()
-    ref = h16(Ap @ Wp.t() + bp + res)
-    close(xs, ref)
-    st = stat.cpu().view(parts, M, 2).sum(dim=0)
-    assert torch.isfinite(st).all(), "a statistics slot was not written"
-    r1, r2 = xs.double().sum(dim=1), (xs.double() ** 2).sum(dim=1)
-    e1 = ((st[:, 0].double() - r1).abs() / (xs.double().abs().sum(dim=1) + 1e-6)).max().item()
-    e2 = ((st[:, 1].double() - r2).abs() / (r2 + 1e-6)).max().item()
-    print(f"row statistics vs float64: sum {e1:.2e} (of sum |x|), sum of squares {e2:.2e} relative")
-    assert e1 < 2e-6 and e2 < 2e-6      # fp32 accumulation of exact f16 products (v_dot2c_f32_f16), a few hundred terms
+    for far in (False, True):
+        g = torch.Generator().manual_seed(5 + M + C + pvariant + 1000 * far)
+        Kp = 128
+        Ap = h16(torch.randn(M, Kp, generator=g))
+        Wp = h16(torch.randn(C, Kp, generator=g) * Kp ** -0.5)
+        bp = torch.randn(C, generator=g)
+        if far:
+            sign = torch.where(torch.rand(M, 1, generator=g) < 0.5, -1.0, 1.0)
+            res = h16(sign * 300.0 + torch.randn(M, C, generator=g) * 2.8)      # + the unit-variance GEMM part: sigma = 3
+        else:
+            res = h16(torch.randn(M, C, generator=g) * 3 + 2.0)
+        x, stat, parts = _producer(hip, Ap, Wp, bp, res, M, C, Kp, pvariant)
+        xs = x.float().cpu()
+        ref = h16(Ap @ Wp.t() + bp + res)
+        close(xs, ref)
+        st = stat.cpu().view(parts, M, 2).double()
+        assert torch.isfinite(st).all(), "a statistics slot was not written"
+        bn = C if parts == 1 else next(w for w in (64, 128, 256) if (C + w - 1) // w == parts)
+        e1 = e2 = 0.0
+        for t in range(parts):
+            v = xs[:, t * bn:min(C, (t + 1) * bn)].double()
+            n = v.shape[1]
+            s64, a64 = v.sum(dim=1), v.mean(dim=1)
+            m2 = ((v - a64[:, None]) ** 2).sum(dim=1)
+            e1 = max(e1, ((st[t, :, 0] - s64).abs() / (v.abs().sum(dim=1) + 1e-6)).max().item())
+            # the kernel sums squares of d = x - pivot (exact in fp32), the pivot being the tile's first value: a sum of the size
+            # M2_t + n (pivot - mean_t)^2 carries the fp32 accumulation error, and the (sum d)^2 / n it subtracts as much again
+            scale = m2 + 2 * n * (v[:, 0] - a64) ** 2
+            e2 = max(e2, ((st[t, :, 1] - m2).abs() / (scale + 1e-6)).max().item())
+            assert (st[t, :, 1] >= 0).all()
+        print(f"row statistics vs float64 ({'far from zero' if far else 'near zero'}): tile sums {e1:.2e} (of sum |x|), "
+              f"centred sums of squares {e2:.2e} (of M2 + 2 n (pivot - mean)^2)")
+        assert e1 < 2e-6 and e2 < 2e-6      # fp32 accumulation of exact differences of halfs, at most 128 terms
 
 
 CASES = [

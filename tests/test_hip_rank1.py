@@ -151,7 +151,7 @@ def test_denoise_loop_selects_rank1_plan(tiny):
 def test_gemm_lnx_requested_stat_parts(hiplib):
     """rcdm_gemm_lnx with a stat_parts other than the shape's own tile choice (rcdm_gemm_lnx_parts_ok): a row subset of a
     projection rewrites its rows' statistics inside the buffer the full-row launch filled — same slot count, same plane
-    stride, the other rows untouched; the sums against float64."""
+    stride, the other rows untouched; the slots (tile sum, centred sum of squares) against float64."""
     from rcdms_amd.engine import Plan, emit_gemm, Rows
     torch.manual_seed(0)
     M, C, r0, n = 10240, 640, 2048, 2048
@@ -172,13 +172,22 @@ def test_gemm_lnx_requested_stat_parts(hiplib):
     plan.run()
     torch.cuda.synchronize()
     o = out.buf.t.view(torch.float16)[:M * C].view(M, C).double()
-    stat = st.buf.t.view(torch.float32)[:st.parts * st.rows * 2].view(st.parts, st.rows, 2).double().sum(dim=0)
+    slots = st.buf.t.view(torch.float32)[:st.parts * st.rows * 2].view(st.parts, st.rows, 2).double()
+    stat = slots.sum(dim=0)
     ref = a.float() @ W.float().t()
     exp = (ref + bias).half()
     exp[r0:r0 + n] = (ref[r0:r0 + n] + 2 * bias).half()
     assert (o - exp.double()).abs().max() <= 2e-2
     assert torch.allclose(stat[:, 0], o.sum(dim=1), rtol=2e-6, atol=1e-3)
-    assert torch.allclose(stat[:, 1], (o * o).sum(dim=1), rtol=2e-6, atol=1e-3)
+    # a slot's second half is the centred sum of squares of its column tile (the slot rule: igemm_args.h), summed about the
+    # tile's first value: 2e-6 of that sum's size, as the sums above
+    bn = C if st.parts == 1 else next(w for w in (64, 128, 256) if (C + w - 1) // w == st.parts)
+    for t in range(st.parts):
+        v = o[:, t * bn:min(C, (t + 1) * bn)]
+        mean = v.mean(dim=1)
+        m2 = ((v - mean[:, None]) ** 2).sum(dim=1)
+        size = m2 + 2 * v.shape[1] * (v[:, 0] - mean) ** 2
+        assert ((slots[t, :, 1] - m2).abs() <= 2e-6 * size + 1e-3).all()
 
 
 # ---- numerics report + the third weight family --------------------------------------------------------------------------
