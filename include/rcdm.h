@@ -1316,6 +1316,60 @@ typedef struct {
 int rcdm_image_bilinear_rows(const rcdm_bilinear_desc* d, const void* src_u8, void* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LPIPS: the learned perceptual distance of Zhang et al. (The Unreasonable Effectiveness of Deep Features as a Perceptual
+ * Metric, 2018), v0.1, over a VGG-16 or AlexNet tower built from rcdm_conv2d / rcdm_pool2d; rcdms_amd/lpips.py is the caller.
+ * csrc/lpips_core.h holds the head's arithmetic and its summation orders, shared with tools/lpips_host.cpp; restated from the
+ * paper and the lpips package's published forward, not pinned against the package.  Checks as for the conv2d block: every one
+ * before anything is launched, RCDM_EINVAL for a null or misaligned pointer, a size <= 0 or an ld below the channel count,
+ * RCDM_ESHAPE for a shape limit.  Row and byte offsets are 64-bit.
+ *
+ * rcdm_lpips_head: one tap of `pairs` frame pairs.  a and b are f16 pixel rows [pairs * h * w][lda | ldb] of c channels,
+ *   post-ReLU; they may be the two halves of one buffer of 2 pairs frames (b = a + pairs h w lda).  lin: fp32 [c], >= 0.
+ *   Per pixel, in fp32 on the widened f16 values:  na = sqrt(sum_c a_c^2) + 1e-10 (epsilon after the root), nb likewise,
+ *   v = sum_c lin_c (a_c / na - b_c / nb)^2 with true divisions; an all-zero pixel gives 0 / 1e-10 = 0, finite.
+ *   out[p] = (sum over the h w pixels of pair p of v) / (h w) in float64: the pixel values of a tile of 64 pixels go through
+ *   a binary tree in float64, the tile partials of a pair through the fixed sum of frechet_core.h, one float64 division
+ *   (lpips_core.h has the orders).  Two launches (tile partials into the workspace, then one workgroup per pair); no atomics,
+ *   no memset: the same input gives the same bits for every grid size.  blocks: the grid of the first launch, 0 = the
+ *   library's choice (for tests of that property).  Every feature row is read once; nothing but the tile partials is written.
+ *   Limits (RCDM_ESHAPE): c % 8 == 0, c <= 512, lda % 8 == 0, ldb % 8 == 0, pairs <= 65535, sides <= 8192; a, b, lin and the
+ *   workspace 16-byte aligned, out 8-byte aligned.  workspace: rcdm_lpips_head_workspace_bytes (0 for a bad descriptor);
+ *   smaller is RCDM_EWORKSPACE.
+ * rcdm_lpips_input_rows: n uint8 HWC frames (3 channels; src_pitch / src_stride bytes between rows / frames, as
+ *   rcdm_bilinear_desc) -> the towers' f16 input rows with the scaling layer applied:
+ *     value = f16(fma(u8 / 255, mul[ch], add[ch]))   — a division, ONE fused multiply-add (one rounding to fp32), one rounding
+ *   to f16 (not the two-rounding form of rcdm_image_bilinear_rows); with mul = 2 / scale and add = (-1 - shift) / scale this is
+ *   (2 u8 / 255 - 1 - shift) / scale of LPIPS's ScalingLayer.
+ *     space_to_depth == 1   rows [n * in_h * in_w][ld]: channels 0 .. 2 the pixel, 3 .. 7 zeros (rcdm_conv2d's padded image)
+ *     space_to_depth == 4   AlexNet's Conv2d(3, 64, 11, stride=4, padding=2) as a 3 x 3 stride-1 pad-0 rcdm_conv2d: rows
+ *                           [n * (h_out + 2) * (w_out + 2)][ld] of 48 channels, h_out = (in_h - 7) / 4 + 1 (sides >= 7),
+ *                           Q[n][Y][X][(dy 4 + dx) 3 + ch] = x[n][4 Y + dy - 2][4 X + dx - 2][ch], 0 outside the image (torch
+ *                           pads the scaled tensor with zeros); the weights are W'[o][(KY 3 + KX) 48 + (dy 4 + dx) 3 + ch] =
+ *                           W[o][ch][4 KY + dy][4 KX + dx], zeros for the twelfth row and column.  Exact, K = 432 against 363.
+ *   Columns at and above 8 (48) of a wider row are left alone.  ld % 8 == 0, dst 16-byte aligned.
+ *   rcdm_lpips_input_sides: the output sides and channel count of a descriptor (the same checks).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t lda, ldb;                /* row strides of a / b in elements */
+  int32_t pairs, h, w, c;
+  int32_t blocks;                  /* grid of the first launch; 0: the library's choice */
+  int32_t reserved;
+} rcdm_lpips_head_desc;
+size_t rcdm_lpips_head_workspace_bytes(const rcdm_lpips_head_desc* d);
+int rcdm_lpips_head(const rcdm_lpips_head_desc* d, const void* a, const void* b, const float* lin, double* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
+typedef struct {
+  int64_t src_pitch, src_stride;   /* bytes between source rows / source frames */
+  int32_t n, in_h, in_w;
+  int32_t space_to_depth;          /* 1 or 4 */
+  int32_t ld;
+  float mul[3], add[3];            /* per channel */
+} rcdm_lpips_input_desc;
+int rcdm_lpips_input_sides(const rcdm_lpips_input_desc* d, int32_t* out_h, int32_t* out_w, int32_t* channels);
+int rcdm_lpips_input_rows(const rcdm_lpips_input_desc* d, const void* src_u8, void* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph plumbing: capture the ~10^3 launches of one denoising step once, replay per step.
  * ---------------------------------------------------------------------------------------------- */
 int rcdm_graph_begin_capture(void* stream);

@@ -113,6 +113,16 @@ class BilinearDesc(C.Structure):
                 ("scale", C.c_float * 3), ("shift", C.c_float * 3)]
 
 
+class LpipsHeadDesc(C.Structure):
+    _fields_ = [("lda", C.c_int64), ("ldb", C.c_int64), ("pairs", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
+                ("blocks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LpipsInputDesc(C.Structure):
+    _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("n", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32),
+                ("space_to_depth", C.c_int32), ("ld", C.c_int32), ("mul", C.c_float * 3), ("add", C.c_float * 3)]
+
+
 class PngDesc(C.Structure):
     _fields_ = [("src_pitch", C.c_int64), ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("n", C.c_int32),
                 ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32)]
@@ -201,6 +211,7 @@ IMAGE_TILE = 32                                         # RCDM_IMAGE_TILE
 IMAGE_U8, IMAGE_F32_NCHW, IMAGE_F16_ROWS = 0, 1, 2      # ResampleDesc.mode
 FRAMES_F16_ROWS, FRAMES_F32_NCHW = 0, 1                 # FramesU8Desc.src_kind
 POOL_MAX, POOL_AVG_INCLUDE_PAD, POOL_AVG_EXCLUDE_PAD = 0, 1, 2   # Pool2dDesc.mode
+LPIPS_MAX_C, LPIPS_TILE, LPIPS_MAX_PAIRS = 512, 64, 65535       # lp::MAX_C, TILE, MAX_PAIRS
 
 # every symbol include/rcdm.h declares: name -> (restype, argtypes)
 _P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
@@ -278,6 +289,10 @@ SYMBOLS = {
     "rcdm_pool2d": (C.c_int, [C.POINTER(Pool2dDesc), _P, _P, _P]),
     "rcdm_global_avgpool": (C.c_int, [_I, _I, _I, _P, C.c_int64, _P, C.c_int64, _P]),
     "rcdm_image_bilinear_rows": (C.c_int, [C.POINTER(BilinearDesc), _P, _P, _P]),
+    "rcdm_lpips_head_workspace_bytes": (_SZ, [C.POINTER(LpipsHeadDesc)]),
+    "rcdm_lpips_head": (C.c_int, [C.POINTER(LpipsHeadDesc), _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_lpips_input_sides": (C.c_int, [C.POINTER(LpipsInputDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rcdm_lpips_input_rows": (C.c_int, [C.POINTER(LpipsInputDesc), _P, _P, _P]),
     "rcdm_png_bound": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_workspace_bytes": (_SZ, [C.POINTER(PngDesc)]),
     "rcdm_png_encode": (C.c_int, [C.POINTER(PngDesc), _P, _P, _P, _P, _P]),
@@ -656,6 +671,27 @@ def global_avgpool(n_img, rows_per_img, c, x, ld, out, ldo, stream=None):
 def image_bilinear_rows(desc, src, dst, stream=None):
     _check(load().rcdm_image_bilinear_rows(C.byref(desc), src, dst, stream_ptr() if stream is None else stream),
            "rcdm_image_bilinear_rows")
+
+
+def lpips_head_workspace_bytes(desc):
+    return load().rcdm_lpips_head_workspace_bytes(C.byref(desc))
+
+
+def lpips_head(desc, a, b, lin, out, workspace, workspace_bytes, stream=None):
+    _check(load().rcdm_lpips_head(C.byref(desc), a, b, lin, out, workspace, workspace_bytes,
+                                  stream_ptr() if stream is None else stream), "rcdm_lpips_head")
+
+
+def lpips_input_sides(desc):
+    """-> (out_h, out_w, channels) of the rows rcdm_lpips_input_rows writes for this descriptor."""
+    h, w, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(load().rcdm_lpips_input_sides(C.byref(desc), C.byref(h), C.byref(w), C.byref(c)), "rcdm_lpips_input_sides")
+    return h.value, w.value, c.value
+
+
+def lpips_input_rows(desc, src, dst, stream=None):
+    _check(load().rcdm_lpips_input_rows(C.byref(desc), src, dst, stream_ptr() if stream is None else stream),
+           "rcdm_lpips_input_rows")
 
 
 def png_bound(desc):

@@ -100,10 +100,11 @@ class StoryResult:
     ssim: Optional[torch.Tensor] = None    # (S, 5) float64, generated frame against its resized target (metrics=("ssim",))
     psnr: Optional[torch.Tensor] = None    # (S, 5) float64, inf for identical frames (metrics=("psnr",))
     clip_i: Optional[torch.Tensor] = None  # (S, 5) cosine of the generated frames' CLIP embeddings and target_embeds ("clip_i")
+    lpips: Optional[torch.Tensor] = None   # (S, 5) float64, LPIPS of the generated frame and its resized target (metrics=("lpips",))
     frames_u8: Optional[torch.Tensor] = None   # (S, 5, H, W, 3) device uint8: the kept frames a stage-2 autoregressive run handed on
 
 
-METRICS = ("ssim", "psnr", "clip_i")
+METRICS = ("ssim", "psnr", "clip_i", "lpips")
 FEATURE_SOURCES = ("clip", "inception")
 AUTOREG_OUTPUTS = ("tensor", "uint8", "png")
 
@@ -157,12 +158,13 @@ class StoryRunner:
     [-1, 1] (default rcdms_amd.image.FrameTransform at the UNet's sample size); inception: an
     rcdms_amd.inception.InceptionV3Features (uint8 frames -> (n, 2048) fp32), the extractor of feature_source="inception";
     classifier: a second InceptionV3Features, the character classifier whose logits label_counts scores (other weights than the
-    FID network's, usually preprocess="pillow")."""
+    FID network's, usually preprocess="pillow").
+    lpips: an rcdms_amd.lpips.LpipsNet, the network behind metrics=("lpips",)."""
 
     def __init__(self, prior_pipe, stage2_pipe, image_encoder, clip_processor=None, frame_transform=None, inception=None,
-                 classifier=None):
+                 classifier=None, lpips=None):
         self.prior_pipe, self.stage2_pipe, self.image_encoder = prior_pipe, stage2_pipe, image_encoder
-        self.inception, self.classifier = inception, classifier
+        self.inception, self.classifier, self.lpips = inception, classifier, lpips
         if clip_processor is None:
             from .image import ClipImageProcessor
             size = int(image_encoder.config.image_size)
@@ -218,10 +220,12 @@ class StoryRunner:
         drivers do).  stage2: run stage 2 (default: in "continue" mode when the runner has a stage-2 pipeline).  save_dir /
         indices: also write each story's stage-1 embeddings as `{index}_{j}.npy` / `{index}.npy` (indices default 0..S-1).
         guidance_rescale / eta: stage 2's sampling arguments (RCDMsPipeline.__call__); the stage-1 prior has neither.
-        metrics: any of "ssim", "psnr", "clip_i" — per-frame figures of the generated frames against the five given frames
+        metrics: any of "ssim", "psnr", "clip_i", "lpips" — per-frame figures of the generated frames against the five given frames
         resized to the stage-2 size with Pillow's bilinear filter (the driver's vis_augment, stage2…:390-396), in the result's
-        fields of those names, computed on the device (rcdms_amd.metrics; "clip_i" is one more vision forward).  They need a
-        stage-2 run with output_type="uint8".  metrics=(): nothing more is launched.
+        fields of those names, computed on the device (rcdms_amd.metrics; "clip_i" is one more vision forward; "lpips" runs the
+        runner's `lpips` network, rcdms_amd.lpips.LpipsNet, on the same resized targets "ssim" / "psnr" use — without one it is a
+        ValueError before anything is launched).  They need a stage-2 run with output_type="uint8".  metrics=(): nothing more
+        is launched.
         feature_stats: (generated, reference), two rcdms_amd.frechet.FeatureStats of the embedding width: the CLIP embeddings of
         the 5 S generated frames are added to `generated` (the forward "clip_i" runs, done once when both are asked for) and
         target_embeds to `reference`, for a set-level Fréchet distance (frechet_distance; a CLIP-FD) over as many calls as the
@@ -264,6 +268,8 @@ class StoryRunner:
         for m in metrics:
             if m not in METRICS:
                 raise ValueError(f"metric {m!r}: any of {METRICS}")
+        if "lpips" in metrics and self.lpips is None:
+            raise ValueError('metrics=("lpips",) needs a network: build the runner with lpips=LpipsNet(...)')
         if mode not in ("continue", "visualization"):
             raise ValueError("check mode")                                      # stage1…:180
         if feature_source not in FEATURE_SOURCES:
@@ -472,8 +478,13 @@ class StoryRunner:
             raise ValueError(f'feature_source="inception" reads uint8 frames, got {videos.dtype}')
         S = videos.shape[0]
         out = {}
+        if "lpips" in metrics and self.lpips is None:
+            raise ValueError('metrics=("lpips",) needs a network: build the runner with lpips=LpipsNet(...)')
+        targets = self.target_frames(frames) if any(m in metrics for m in ("ssim", "psnr", "lpips")) else None
+        if "lpips" in metrics:
+            out["lpips"] = self.lpips(videos, targets)
         if "ssim" in metrics or "psnr" in metrics:
-            fm = frame_metrics(videos, self.target_frames(frames))
+            fm = frame_metrics(videos, targets)
             if "ssim" in metrics:
                 out["ssim"] = fm.ssim.view(S, FRAMES)
             if "psnr" in metrics:
