@@ -54,9 +54,15 @@ int rcdm_num_cus();
 // v_rcp_f32 (1 ulp) instead of an IEEE division: `a / b` and __frcp_rn expand to ~12 VALU ops on gfx950
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // exact-form (erf) GELU, as diffusers GEGLU.gelu -> F.gelu(approximate="none"): x * Phi(x) with erf by Abramowitz &
-// Stegun 7.1.25 (three terms, |error of erf| <= 2.5e-5, so |error of the GELU| <= 1.25e-5 |x|: a fortieth of the f16 rounding
-// of the value it is about to be stored as; round 4 — rounds 1-3 used the five-term 7.1.26 at 1.5e-7, two more packed FMAs per
-// pair; libm erff's ~40 VALU ops made the GEGLU epilogue VALU-bound).  With z = |x| / sqrt(2), t = 1 / (1 + p z),
+// Stegun 7.1.25 (three terms, |error of erf| <= 2.5e-5, so |error of the GELU| <= 1.25e-5 |x| ABSOLUTE: a fortieth of the f16
+// rounding of x, not of the value it is about to be stored as.  Measured on every f16 x (tests/act_sweep.py): the fp32 form
+// uses at most 0.84 of that bound (at x = -2.293); on gates in [-6, -2], where the GELU itself is small, it is up to 20.8 f16
+// ulps of the true value away from it (x = -4.012: true -1.209e-4, this form -1.222e-4; 21 ulps once rounded to f16).  The
+// fused feed-forward (rowff.hip, geglu_slice) keeps the five-term 7.1.26 at 1.5e-7, within 0.97 ulp everywhere, so the
+// fused and the unfused feed-forward of one layer differ by up to ~21 ulps on gates in [-6, -2]: |h| times 2.6e-5 at
+// the most, far below the rounding of a GEMM2 input of ordinary size.  Round 4 — rounds 1-3 used the five-term form here
+// too, two more packed FMAs per pair; libm erff's ~40 VALU ops made the GEGLU epilogue VALU-bound).
+// With z = |x| / sqrt(2), t = 1 / (1 + p z),
 // q = (1 - erf(z)) / 2 = poly(t) * exp(-z^2) / 2:   gelu(x) = max(x, 0) - |x| * q
 // (sqrt(2) and the 1/2 are folded into the constants).  Written on pairs: v_pk_fma_f32 / v_pk_mul_f32 do two fp32
 // lanes per instruction, so a pair costs 4 packed ops + 2 rcp + 2 exp + 2 max + 3 mul; the epilogues of the K = 320 GEMMs
@@ -104,7 +110,7 @@ __device__ __forceinline__ void gelu8(float (&v)[8]) {
 // |x| large: 2^big = inf, q = 0.
 __device__ __forceinline__ f32x2 quick_gelu2(f32x2 x) {
   const f32x2 ax = __builtin_elementwise_abs(x);
-  const f32x2 z = ax * splat2(2.45548296f);
+  const f32x2 z = ax * splat2(2.45546696f);  // 1.702 * log2(e)  (was 2.45548296: two digits transposed, 1.702011 in effect)
   const f32x2 d = {1.0f + __builtin_amdgcn_exp2f(z.x), 1.0f + __builtin_amdgcn_exp2f(z.y)};
   const f32x2 q = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
   return __builtin_elementwise_fma(-ax, q, __builtin_elementwise_max(x, splat2(0.0f)));

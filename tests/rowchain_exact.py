@@ -26,8 +26,9 @@ argument: one misplaced term each (MUTATIONS), for the host test to show that ex
 close() of tests/test_hip_kernels.py lets through on that suite's random operands.
 
 Deliberately NOT pinned here, and left to the tolerance tests (tests/test_hip_rowff.py, tests/test_hip_motion_fused.py): the
-pe row map of the frame-major tail (tail 4 runs without pe here), GELU between its saturated ends, and LayerNorm on rows that
-are not two-valued (on two-valued f16 rows even E[x^2] - mean^2 in fp32 is exact: see MUTATIONS["ln_var_e2"])."""
+pe row map of the frame-major tail (tail 4 runs without pe here), GELU between its saturated ends (pinned value by value by
+tests/act_sweep.py / tests/test_hip_act_sweep.py), and LayerNorm on rows that are not two-valued (on two-valued f16 rows
+even E[x^2] - mean^2 in fp32 is exact: see MUTATIONS["ln_var_e2"])."""
 import math
 
 import numpy as np
