@@ -1189,6 +1189,40 @@ int rcdm_inception_score(const rcdm_isc_desc* d, const void* logits, const int32
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Denoising objective: what surrounds the UNet when the stage-2 training quantity F.mse_loss(noise_pred, noise) is evaluated
+ * at one random timestep per story (train_stage2.py:420-486), without an fp32 NCFHW tensor on either side of the network.
+ * csrc/objective_core.h holds every rule and the order of every sum, shared with tools/objective_host.cpp.  Restated from
+ * train_stage2.py and the diffusers DDPMScheduler.add_noise formula; not pinned against diffusers.  Forward only.
+ *   rcdm_diffuse_assemble   one launch.  x0, noise, masked: fp32 (B,4,f,H,W); mask: fp32 (B,1,f,H,W); offs: fp32 (B,4,f) or
+ *                 null — the noise_offset term of train_stage2.py:445-449, n = noise + offs_scale * offs[b][c][f], the product
+ *                 and the sum each rounded to fp32; t: int64[B] ON THE DEVICE, never read by the host; table: fp32 [T][2] =
+ *                 (sqrt(a_t), sqrt(1 - a_t)).  out rows [(B*f*H*W)][ld] f16 in rcdm_assemble_input's channel layout:
+ *                 channels 0..3 = f16((sa * x0) + (s1m * n)), every product and sum rounded to fp32 on its own and never
+ *                 contracted into an fma — the bits of torch's mul, mul, add and .half() —, channel 4 = mask, 5..8 = masked,
+ *                 9..c_pad-1 = 0; columns c_pad..ld are not touched.  A story whose t is outside [0, T) reads nothing from
+ *                 the table and gets the f16 NaN 0x7E00 in channels 0..3.  A row is stored as c_pad / 8 16-byte vectors.
+ *   rcdm_eps_sqerr  out[B][f] (float64) = sum over the frame's 4 H W elements of (double(eps) - double(n))^2; eps: the UNet's f16
+ *                 output rows [(B*f*H*W)][ld], channels 0..3; n formed from noise / offs / offs_scale as above.  Two launches
+ *                 (chunks of 256 pixels of a frame, then a fold), fixed order: a pixel's four channels ascending, a binary
+ *                 tree over the chunk, the chunk sums ascending.  No atomics, no memset: the same bits for every `blocks`
+ *                 (the grid of the first launch; 0: the library chooses, else 1 .. 65535) and on every rerun.  NaN and inf
+ *                 propagate.
+ *     workspace   B * f * ceil(H W / 256) doubles.
+ * RCDM_EINVAL: a null pointer (offs may be null), a dimension or T below 1, blocks outside 0 .. 65535, a misaligned pointer
+ * (fp32 operands at 4, t, out[B][f], eps and the workspace at 8, the input rows at 16).  RCDM_ESHAPE: B f H W >= 2^31; c_pad
+ * below 16, above 1024 or no multiple of 8, ld below c_pad or no multiple of 8 (rcdm_diffuse_assemble); ld below 4 or no
+ * multiple of 4 (rcdm_eps_sqerr).  RCDM_EWORKSPACE: workspace null or short.  All checked before anything is launched;
+ * rcdm_eps_sqerr_workspace_bytes gives 0 for what would be refused.
+ * ---------------------------------------------------------------------------------------------- */
+int rcdm_diffuse_assemble(const float* x0, const float* noise, const float* offs, float offs_scale, const int64_t* t,
+                          const float* table, int32_t T, const float* mask, const float* masked, int32_t B, int32_t frames,
+                          int32_t H, int32_t W, void* out, int32_t ld, int32_t c_pad, void* stream);
+size_t rcdm_eps_sqerr_workspace_bytes(int32_t B, int32_t frames, int32_t H, int32_t W);
+int rcdm_eps_sqerr(const void* eps, int32_t ld, const float* noise, const float* offs, float offs_scale, int32_t B,
+                   int32_t frames, int32_t H, int32_t W, int32_t blocks, double* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CLIP tokenizer: n ASCII captions on the device -> the rows transformers.CLIPTokenizer(...)(texts, padding="max_length",
  * max_length=..., truncation=..., return_tensors="pt") returns, what both pipelines ask of their tokenizer
  * (RCDMs_pipeline.py:_encode_prompt, prior_pipeline.py:_encode_prompt), plus what the text encoder otherwise reads back to the

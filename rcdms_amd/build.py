@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "librcdm_hip.so")
-SOURCES = ["igemm.hip", "igemm_plan.hip", "igemm8.hip", "igemm16.hip", "wino.hip", "rowff.hip", "norm.hip", "attn.hip", "attn_wide.hip", "misc.hip", "guide.hip", "image.hip", "conv2d.hip", "lpips.hip", "png.hip", "png_decode.hip", "metrics.hip", "frechet.hip", "kid.hip", "prdc.hip", "scores.hip", "tokenize.hip", "runtime.hip", "comm.hip"]
+SOURCES = ["igemm.hip", "igemm_plan.hip", "igemm8.hip", "igemm16.hip", "wino.hip", "rowff.hip", "norm.hip", "attn.hip", "attn_wide.hip", "misc.hip", "guide.hip", "image.hip", "conv2d.hip", "lpips.hip", "png.hip", "png_decode.hip", "metrics.hip", "frechet.hip", "kid.hip", "prdc.hip", "scores.hip", "objective.hip", "tokenize.hip", "runtime.hip", "comm.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar f32 adds / muls into v_pk_*_f32, which issue slower than
 # the scalars they replace next to MFMAs on gfx950 (measured +0.5 % end to end without it); the packed forms that do pay

@@ -326,6 +326,9 @@ SYMBOLS = {
     "rcdm_label_counts": (C.c_int, [C.POINTER(LabelDesc), _P, _P, _P, _P, _P, _SZ, _P]),
     "rcdm_inception_score_workspace_bytes": (_SZ, [C.POINTER(IscDesc)]),
     "rcdm_inception_score": (C.c_int, [C.POINTER(IscDesc), _P, _P, _P, _P, _P, _SZ, _P]),
+    "rcdm_diffuse_assemble": (C.c_int, [_P, _P, _P, _F, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "rcdm_eps_sqerr_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "rcdm_eps_sqerr": (C.c_int, [_P, _I, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "rcdm_tok_pair_hash": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "rcdm_clip_tokenize_workspace_bytes": (_SZ, [C.POINTER(TokenizeDesc)]),
     "rcdm_clip_tokenize": (C.c_int, [C.POINTER(TokenizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -845,6 +848,21 @@ def inception_score_workspace_bytes(desc):
 def inception_score(desc, logits, order, kl_out, row_h, workspace, workspace_bytes, stream=None):
     _check(load().rcdm_inception_score(C.byref(desc), logits, order, kl_out, row_h, workspace, workspace_bytes, _st(stream)),
            "rcdm_inception_score")
+
+
+def diffuse_assemble(x0, noise, offs, offs_scale, t, table, T, mask, masked, B, frames, H, W, out, ld, c_pad, stream=None):
+    """offs: 0 (no noise offset) or the address of the fp32 (B,4,f) draw; t: int64[B] on the device."""
+    _check(load().rcdm_diffuse_assemble(x0, noise, offs, offs_scale, t, table, T, mask, masked, B, frames, H, W, out, ld, c_pad,
+                                        _st(stream)), "rcdm_diffuse_assemble")
+
+
+def eps_sqerr_workspace_bytes(B, frames, H, W):
+    return int(load().rcdm_eps_sqerr_workspace_bytes(B, frames, H, W))
+
+
+def eps_sqerr(eps, ld, noise, offs, offs_scale, B, frames, H, W, out, workspace, workspace_bytes, blocks=0, stream=None):
+    _check(load().rcdm_eps_sqerr(eps, ld, noise, offs, offs_scale, B, frames, H, W, blocks, out, workspace, workspace_bytes,
+                                 _st(stream)), "rcdm_eps_sqerr")
 
 
 def frame_metrics_workspace_bytes(desc):

@@ -450,6 +450,53 @@ def _train_betas(c):
     raise NotImplementedError(f"beta_schedule {c.beta_schedule!r}: only 'linear', 'scaled_linear' and trained_betas")
 
 
+class DDPMScheduler:
+    """The training-side scheduler (reference: `DDPMScheduler(...)` at train_stage2.py:299-301, `add_noise` at :457): the
+    forward-diffusion step only, no `step()`.
+
+    Arithmetic of diffusers==0.24.0 `DDPMScheduler.add_noise` (not vendored by the reference, not installed here: restated —
+    "parity unpinned", pinned by closed-form tests in tests/test_objective_host.py):
+        noisy = alphas_cumprod[t] ** 0.5 * x0 + (1 - alphas_cumprod[t]) ** 0.5 * noise,   alphas_cumprod fp32.
+    The two coefficients of every training timestep are formed ONCE on the host by those expressions (`_table`, fp32 [T][2]);
+    `add_noise` (torch) and rcdm_diffuse_assemble (through `noise_table(device)`) both read that table, so the two use the same
+    coefficient bits whatever the device's pow rounds to."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None):
+        self._internal_dict = _FrozenDict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                          beta_schedule=beta_schedule, trained_betas=trained_betas)
+        self.betas = _train_betas(self.config)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        ac = self.alphas_cumprod
+        self._table = torch.stack([ac ** 0.5, (1 - ac) ** 0.5], dim=1).contiguous()
+        self._tables = {}
+        self.init_noise_sigma = 1.0
+        self.timesteps = torch.arange(len(self.betas) - 1, -1, -1, dtype=torch.int64)
+
+    @property
+    def config(self):
+        return self._internal_dict
+
+    def noise_table(self, device=None):
+        """fp32 [T][2] = (alphas_cumprod ** 0.5, (1 - alphas_cumprod) ** 0.5), computed on the host; device: where a copy is
+        kept (uploaded once per device)."""
+        if device is None:
+            return self._table
+        device = torch.device(device)
+        if device not in self._tables:
+            self._tables[device] = self._table.to(device)
+        return self._tables[device]
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """timesteps: int64, one per leading element, each in [0, T)."""
+        tab = self.noise_table(original_samples.device).to(original_samples.dtype)
+        shape = (-1,) + (1,) * (original_samples.dim() - 1)
+        t = timesteps.to(original_samples.device)
+        sqrt_alpha_prod = tab[t, 0].reshape(shape)
+        sqrt_one_minus_alpha_prod = tab[t, 1].reshape(shape)
+        return sqrt_alpha_prod * original_samples + sqrt_one_minus_alpha_prod * noise
+
+
 def _convert_to_karras(in_sigmas, n, sigma_min=None, sigma_max=None):
     """Karras et al. (2022) eq. (5), rho = 7, between the given endpoints (default: the ends of in_sigmas)."""
     lo = float(in_sigmas[-1]) if sigma_min is None else float(sigma_min)

@@ -414,3 +414,27 @@ class UNetProgram:
         x.record_stream(self.stream)
         out.record_stream(self.stream)
         return out
+
+    def forward_rows(self, fill, timestep, ctx, read, use_graph=True):
+        """As forward, with the input rows written by `fill(self.x_in)` and the output rows consumed by `read(self.eps_out)`,
+        both on the program's stream, in place of the two layout conversions (rcdms_amd.objective).  timestep: a number or a
+        tensor of b of them; a device tensor is copied on the device, never read back.  The caller keeps what fill and read
+        touch alive across the call (record_stream on the program's stream where it frees them early).  Returns read's value."""
+        self.set_context(ctx)
+        t = torch.as_tensor(timestep, device=self.device).to(torch.float32).reshape(-1)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.t_dev.copy_(t.expand(self.b))
+            fill(self.x_in)
+            if use_graph and self.calls >= 1:
+                if self.graph is None:
+                    self.graph = self.capture()
+                self.graph.launch()
+            else:
+                self.plan.run()
+            self.calls += 1
+            res = read(self.eps_out)
+        cur.wait_stream(self.stream)
+        t.record_stream(self.stream)
+        return res
