@@ -11,13 +11,13 @@
 // epilogue and tile fill run under the other's k-loop — what the one-block-per-CU ping-pong kernel (igemm8.hip) cannot
 // do, which is why that kernel only wins where the k-loop is long.
 //
-// Loop: one s_barrier per 64-deep k-step, 2-stage LDS ring filled by buffer_load ... lds (5 pixel + 5 weight 1-KiB
-// pieces per wave and step, XOR swizzle on the source side as in igemm.hip); the pieces of step g+1 are issued right
-// after the barrier that opens step g.  One tile per block, XCD-aware tile order; epilogue through igemm_epilogue.h.
+// Loop: ring2_tile_loop of igemm_frag16.h, shared with the Winograd GEMM (wino.hip); this file fills its ring by
+// buffer_load ... lds (5 pixel + 5 weight 1-KiB pieces per wave and step, addressing and source-side XOR swizzle from
+// igemm_loader.h).  One tile per block, XCD-aware tile order; epilogue through igemm_epilogue.h.
 #include "common.h"
 #include "igemm_plan.h"
 #include "igemm_loader.h"
-#include "pp_sync.h"
+#include "igemm_frag16.h"
 #include "igemm_epilogue.h"
 #ifndef RCDM_I16_ABLATE
 #define RCDM_I16_ABLATE 0  // debug builds: 1 = no epilogue, 2 = epilogue without global stores, 8 = no DMA after the first stage
@@ -90,16 +90,11 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
     }
   };
 
-  // ---- compute mapping: weights are the A operand, pixels the B operand -> D[channel][pixel]
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int sw = (lane >> 1) & 7;
-  const int koff0 = ((kg ^ sw) << 4), koff1 = (((4 + kg) ^ sw) << 4);
-  const int rowA = (wm * (BM / 2) + l15) * 128, rowB = A_BYTES + (wn * (BN / 2) + l15) * 128;
+  // ---- compute mapping (igemm_frag16.h): weights are the A operand, pixels the B operand -> D[channel][pixel]
+  const Frag16Lanes fl = frag16_lanes(lane);
+  const int l15 = fl.l15, kg = fl.kg;
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  frag16_zero(acc);
 
   // epilogue placement: the tables sit in the ring stage the LAST k-step does not read (stage nkl & 1), the f16 staging tile
   // ([BM] rows of 2 BN + 16 bytes = 53760 B) clear of them: behind the tables when that is stage 0, in front when stage 1
@@ -114,38 +109,7 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
     lx_row0.finish(p.lnx_geo, p.lnx_parts, p.lnx_invC, p.lnx_eps, 0, r_, m_);
     lx_pre = f32x2{r_, m_};
   }
-  for (int g = 0; g < nkl; ++g) {
-    // this wave's pieces of step g have landed (nothing newer is in flight); the barrier makes everybody's visible and
-    // says everybody is done reading the stage of step g-1, which the issue below refills
-    wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-#if !(RCDM_I16_ABLATE & 8)
-    if (g + 1 < nkl) issue(g + 1, (g + 1) & 1);
-#endif
-    const char* sb = smem + (g & 1) * STAGE;
-#if RCDM_PRIO_LOADS   // everything but the MFMA runs of a k-step at raised priority (see igemm8.hip compute())
-    __builtin_amdgcn_s_setprio(3);
-#endif
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int koff = kk ? koff1 : koff0;
-      f16x8 wf[FN], xf[FM];
-#pragma unroll
-      for (int i = 0; i < FN; ++i) wf[i] = *(const f16x8*)(sb + rowB + i * 2048 + koff);
-#pragma unroll
-      for (int j = 0; j < FM; ++j) xf[j] = *(const f16x8*)(sb + rowA + j * 2048 + koff);
-#if RCDM_PRIO_LOADS
-      __builtin_amdgcn_s_setprio(0);
-#endif
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-#if RCDM_PRIO_LOADS
-      __builtin_amdgcn_s_setprio(3);
-#endif
-    }
-  }
+  ring2_tile_loop<BM, BN, FM, FN, (RCDM_I16_ABLATE & 8) != 0>(smem, nkl, wm, wn, lane, issue, acc);
   // the ring stage the last k-step did not read is dead (read by nobody, filled by nobody): the deferred-LayerNorm tables go
   // there NOW, so that the barrier below — which the epilogue needs anyway — publishes them (igemm_epilogue.h
   // lnx_write_tables).  Not inside the loop: an ordinary global load anywhere in its body makes hipcc drain the LDS-DMA
@@ -165,11 +129,9 @@ __global__ __launch_bounds__(256, 2) void igemm16_kernel(const IgemmArgs p) {
   }
 #else
   if constexpr (SLAB) {
-    if (p.slab16) {   // f16 slab: the plain-projection path of the staged epilogue, pointed at this split's slab
-      IgemmArgs q{};
-      q.out = (f16*)p.partial + (size_t)blockIdx.y * p.M * p.N;
-      q.M = p.M; q.N = p.N; q.ldc = p.N; q.epi = 0; q.out_scale = 1.0f; q.dup = 0;
-      tile_epilogue<FM, FN, false, 256, BM, BN, false, false>(q, smem, acc, cm0, cn0, wm * (BM / 2), wn * (BN / 2), l15, kg, t, nullptr);
+    if (p.slab16) {   // f16 slab: this split's
+      slab16_tile_store<FM, FN, 256, BM, BN>((f16*)p.partial + (size_t)blockIdx.y * p.M * p.N, p.M, p.N, smem, acc, cm0, cn0,
+                                             wm * (BM / 2), wn * (BN / 2), l15, kg, t);
       return;
     }
   }

@@ -35,7 +35,7 @@
 #include "common.h"
 #include "igemm_plan.h"
 #include "igemm_loader.h"
-#include "pp_sync.h"
+#include "igemm_frag16.h"
 #include "igemm_epilogue.h"
 
 // cache policy of the two LDS-DMA streams (buffer_load ... lds aux bits: 1 = sc0, 2 = nt, 16 = sc1); experiments only
@@ -145,17 +145,13 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
     }
   };
 
-  // ---- compute mapping: 16x16x32 fragments; weights are the A operand, pixels the B operand -> D[channel][pixel]
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int sw = (lane >> 1) & 7;  // (row >> 1) & 7 of this lane's fragment rows (fragment bases are multiples of 16)
-  const int koff0 = ((kg ^ sw) << 4), koff1 = (((4 + kg) ^ sw) << 4);
+  // ---- compute mapping (igemm_frag16.h): 16x16x32 fragments; weights are the A operand, pixels the B operand -> D[channel][pixel]
+  const Frag16Lanes fl = frag16_lanes(lane);
+  const int l15 = fl.l15, kg = fl.kg;
   const int rowA = (grp * HM + l15) * 128, rowB = W_RING + (wn * (BN / 4) + l15) * 128;
 
   f32x4 acc[FNW][FMW];
-#pragma unroll
-  for (int i = 0; i < FNW; ++i)
-#pragma unroll
-    for (int j = 0; j < FMW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  frag16_zero(acc);
   f16x8 wf[FNW], xf[FMW];
 
 #ifdef RCDM_PP_ABLATE  // debug builds only (rcdms_amd.build.build_variant): 1 no DMA after the prologue, 2 no MFMA, 4 no ds_read
@@ -172,34 +168,11 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
 #endif
   auto load_frags = [&](int aslot, int wslot, int koff) __attribute__((always_inline)) {
     if (no_read) return;
-    const char* sa = smem + aslot * A_BYTES + rowA + koff;
-    const char* sb = smem + wslot * W_BYTES + rowB + koff;
-#pragma unroll
-    for (int i = 0; i < FNW; ++i) wf[i] = *(const f16x8*)(sb + i * 2048);
-#pragma unroll
-    for (int j = 0; j < FMW; ++j) xf[j] = *(const f16x8*)(sa + j * 2048);
+    frag16_load<FNW, FMW>(smem + aslot * A_BYTES + rowA, smem + wslot * W_BYTES + rowB, koff, wf, xf);
   };
   auto compute = [&]() __attribute__((always_inline)) {
     if (no_mfma) return;
-    // The MFMA run at LOW priority, everything else of this wave (the load phases: address arithmetic, ds_read, DMA issue)
-    // at high priority.  The SIMD issues oldest-first among equal priorities, and a wave whose next MFMA waits for the
-    // matrix pipe keeps the other wave's VALU instructions from issuing (tools/ubench/pipe_overlap.hip: a VALU wave beside
-    // two MFMA-streaming waves gets one instruction per 23 clocks at equal priority, one per 6.4 at s_setprio 3, with the
-    // MFMA rate unchanged).  Round 2 had it the other way round (MFMA run at priority 1); -0.05 ms per step.
-#if RCDM_PRIO_LOADS
-    __builtin_amdgcn_s_setprio(0);
-#else
-    __builtin_amdgcn_s_setprio(1);
-#endif
-#pragma unroll
-    for (int i = 0; i < FNW; ++i)
-#pragma unroll
-      for (int j = 0; j < FMW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-#if RCDM_PRIO_LOADS
-    __builtin_amdgcn_s_setprio(3);
-#else
-    __builtin_amdgcn_s_setprio(0);
-#endif
+    frag16_mfma<FNW, FMW, true>(wf, xf, acc);   // (true: with RCDM_PRIO_LOADS == 0 the run is at priority 1, this kernel's round-2 form)
   };
 
   // DMAs this wave has in flight when "its newest pixel part + its newest weight part" are outstanding
@@ -240,9 +213,9 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
       if (issue_first) {
         if (more_p0) issue_px(g + 1);
         __builtin_amdgcn_sched_barrier(0);
-        load_frags(aslot, wslot, koff0);
+        load_frags(aslot, wslot, fl.koff0);
       } else {
-        load_frags(aslot, wslot, koff0);
+        load_frags(aslot, wslot, fl.koff0);
         if (more_p0) issue_px(g + 1);
       }
       wait_lgkm0();
@@ -256,9 +229,9 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
       if (issue_first) {
         if (more_w) issue_w(g + 2);
         __builtin_amdgcn_sched_barrier(0);
-        load_frags(aslot, wslot, koff1);
+        load_frags(aslot, wslot, fl.koff1);
       } else {
-        load_frags(aslot, wslot, koff1);
+        load_frags(aslot, wslot, fl.koff1);
         if (more_w) issue_w(g + 2);
       }
       wait_lgkm0();
@@ -280,9 +253,9 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
       if (issue_first) {
         if (more) issue_w(g + 2);
         __builtin_amdgcn_sched_barrier(0);
-        load_frags(aslot, wslot, koff0);
+        load_frags(aslot, wslot, fl.koff0);
       } else {
-        load_frags(aslot, wslot, koff0);
+        load_frags(aslot, wslot, fl.koff0);
         if (more) issue_w(g + 2);
       }
       wait_lgkm0();
@@ -295,9 +268,9 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(const IgemmArgs p) {
       if (issue_first) {
         if (more) issue_px(g + 2);
         __builtin_amdgcn_sched_barrier(0);
-        load_frags(aslot, wslot, koff1);
+        load_frags(aslot, wslot, fl.koff1);
       } else {
-        load_frags(aslot, wslot, koff1);
+        load_frags(aslot, wslot, fl.koff1);
         if (more) issue_px(g + 2);
       }
       wait_lgkm0();

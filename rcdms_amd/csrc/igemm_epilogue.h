@@ -1,5 +1,5 @@
-// igemm_epilogue.h — tile epilogue shared by the phase-structured implicit-GEMM kernels (igemm8.hip: 8 waves,
-// igemm16.hip: 4 waves).  Called when every wave of the block is past its k-loop: no LDS read and no DMA is outstanding,
+// igemm_epilogue.h — tile epilogue shared by the 16x16x32-fragment tile kernels (igemm8.hip: 8 waves, igemm16.hip: 4 waves,
+// wino.hip: the 4-wave Winograd GEMM, slab stores only).  Called when every wave of the block is past its k-loop: no LDS read and no DMA is outstanding,
 // so the whole dynamic LDS is free for staging.
 // Accumulator layout (v_mfma_f32_16x16x32_f16, weights = A operand): acc[i][j][e] = D[channel col0 + 16 i + 4 kg + e]
 // [pixel row0 + 16 j + l15] of the BM x BN tile at (cm0, cn0).
@@ -422,4 +422,15 @@ __device__ __forceinline__ void tile_epilogue(const IgemmArgs& p, char* stg, f32
       }
     }
   }
+}
+
+// The tile as f16 to a dense [M][N] slab at dst (split-K slabs of the 160x160 kernel, the Winograd GEMM's slabs): accumulators
+// -> f16 tile in LDS at smem -> whole-row 16-byte stores, i.e. the plain-projection path of tile_epilogue.  Same caller contract.
+template <int FMW, int FNW, int NT, int BM, int BN>
+__device__ __forceinline__ void slab16_tile_store(f16* dst, int M, int N, char* smem, f32x4 (&acc)[FNW][FMW], int cm0, int cn0,
+                                                  int row0, int col0, int l15, int kg, int t) {
+  IgemmArgs q{};
+  q.out = dst;
+  q.M = M; q.N = N; q.ldc = N; q.epi = 0; q.out_scale = 1.0f; q.dup = 0;
+  tile_epilogue<FMW, FNW, false, NT, BM, BN, false, false>(q, smem, acc, cm0, cn0, row0, col0, l15, kg, t, nullptr);
 }

@@ -11,8 +11,16 @@
 // beyond num_records of the kernels' buffer resources, so the hardware writes zeros and the loaders have no branches
 constexpr unsigned kIgemmOOB = 0x80000000u;
 
+// Contiguous-run-per-XCD dealing: the hardware deals workgroups to the 8 XCDs round-robin by linear id, so block lin runs
+// on XCD lin & 7 as that XCD's (lin >> 3)-th block.  Returns the index in a sequence of n work items that gives every XCD
+// one contiguous run of it (the first n & 7 runs one item longer): a bijection of [0, n).
+__host__ __device__ __forceinline__ int xcd_run_index(int lin, int n) {
+  const int xcd = lin & 7, q = n >> 3, r = n & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+}
+
 // XCD-aware, L2-blocked tile order: linear tile index lin -> the tile's first row and column.  Block b runs on XCD b%8, so
-// each XCD is given a contiguous run of the tile sequence; the sequence itself walks super-rows of GM row panels column by
+// each XCD is given a contiguous run of the tile sequence (xcd_run_index); the sequence itself walks super-rows of GM row panels column by
 // column (n outer, m inner inside the super-row), so the ~64 tiles an XCD has in flight form a GM x (64/GM) patch: every
 // activation panel is shared by 64/GM tiles and every weight panel by GM tiles *at the same time*.  With plain n-fastest
 // order a wide N (GEGLU: 40-80 column tiles) streams the whole weight matrix through the 4 MB L2 once per row panel:
@@ -20,9 +28,7 @@ constexpr unsigned kIgemmOOB = 0x80000000u;
 template <int BM, int BN>
 __host__ __device__ __forceinline__ void igemm_tile_origin(const IgemmArgs& p, int lin, int& m0, int& n0) {
   constexpr int GM = 8;
-  const int ntiles = p.tilesM * p.tilesN;
-  const int xcd = lin & 7, q = ntiles >> 3, r = ntiles & 7;
-  const int tl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+  const int tl = xcd_run_index(lin, p.tilesM * p.tilesN);
   const int per_group = GM * p.tilesN;
   const int grp = tl / per_group, rem = tl - grp * per_group;
   const int left = p.tilesM - grp * GM;
@@ -123,5 +129,6 @@ __host__ __device__ __forceinline__ unsigned igemm_weight_offset(const IgemmArgs
 }
 
 // Source-side XOR swizzle: the first channel (of the k-step's 64) that the DMA lane with 16-byte chunk index lch brings to
-// tile row `row` — LDS slot (row, lch) holds global chunk lch ^ ((row >> 1) & 7).
+// tile row `row` — LDS slot (row, lch) holds global chunk lch ^ ((row >> 1) & 7).  The read side of the 16x16x32 kernels is
+// frag16_lanes (igemm_frag16.h).
 __host__ __device__ __forceinline__ int igemm_swizzle_chunk(int row, int lch) { return (lch ^ ((row >> 1) & 7)) * 8; }

@@ -10,7 +10,7 @@
 //
 // Three launches: (1) wino_in_kernel — V[pos][tile][c] = (B^T d B)[pos], fp32 arithmetic on the f16 pixels, ONE rounding to
 // f16; optionally the GroupNorm apply + SiLU of the norm in front of the conv (resnet.py:185-186,202) on the way in, so the
-// normalised tensor is never written; (2) wino_gemm_kernel — the 160x160-tile LDS-DMA loop of igemm16.hip over
+// normalised tensor is never written; (2) wino_gemm_kernel — the 160x160-tile fragment loop of igemm_frag16.h over
 // E = 16 (+ 4) batch entries x split-K slices x tiles, dealt to the XCDs as contiguous runs (whole positions per L2), results
 // to slabs [entry][split][tile][N] — f16 through the staged epilogue by default (rcdm_set_wino_slab_f16), fp32 otherwise:
 // entry e < 16 is V[e] (T x K) against U[e] (N x K); entries 16 + 2a + b (only with a second input) are the 1x1 convolution
@@ -25,42 +25,13 @@
 // (rcdm_conv_taps_gather / rcdm_upsample_taps_gather) — Upsample3D (resnet.py:60-79) and conv_out (unet.py:457) as ONE plain
 // GEMM over nine stacked tap planes + a gather.
 #include "common.h"
-#include "igemm_args.h"
-#include "pp_sync.h"
+#include "wino_loader.h"
+#include "igemm_frag16.h"
 #include "igemm_epilogue.h"
 #include "gn_plan.h"
 #include <stdlib.h>
 
 namespace {
-
-struct WinoArgs {
-  // conv geometry
-  const f16* in;
-  const f16* in2;
-  const f16* U;      // f16 [16][N][K]   (rcdm_pack_conv3x3_wino)
-  const f16* W2;     // f16 [N][K2]      (1x1 weight of the second input) or null
-  const float* bias;
-  const float* rowvec;
-  const f16* res;
-  f16* out;
-  f16* V;            // workspace: f16 [16][T][K]
-  float* slab;       // workspace: fp32 (or, slab16 != 0, f16) [E][splits][T][N]
-  int slab16;
-  int n_img, H, W, th, tw, T, N, K, K2;
-  int lda, lda2, ldc, ldr, ldt, rows_per_sample;
-  int epi;
-  float out_scale;
-  int E, splits, nk, nk2, nkps, nkps2, tilesM, tilesN;
-  // GroupNorm (+ SiLU) applied to `in` by the input transform (null: `in` is used as it is)
-  const float* gn_stat;   // [samples][G][2] = (mean, rstd)
-  const float* gn_gamma;
-  const float* gn_beta;
-  int gn_cg, gn_G, gn_rps, gn_silu;
-  // partial statistics of the GroupNorm that reads `out` NEXT, left by the output transform (null: none): one partial
-  // (count, mean, M2) per (sample, group, tile of the sample), the layout gn_finalize_kernel reads with splits = tiles per sample
-  float* go_partial;
-  int go_G, go_cg, go_rps, go_splits;
-};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // (1) input transform.  One thread per (tile, 4-channel group): 16 pixel loads of 8 bytes (zero outside the image — the
@@ -89,7 +60,7 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const WinoArgs p) {
     for (int j = 0; j < 4; ++j) {
       const int y = 2 * ty - 1 + i, x = 2 * tx - 1 + j;
       ok[i][j] = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-      const unsigned off = ok[i][j] ? base + (unsigned)(y * p.W + x) * (unsigned)p.lda * 2u : 0x80000000u;
+      const unsigned off = ok[i][j] ? base + (unsigned)(y * p.W + x) * (unsigned)p.lda * 2u : kIgemmOOB;
       d[i][j].v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
     }
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -150,11 +121,11 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const WinoArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// (2) the batched GEMM: igemm16.hip's loop (160x160 tile, 4 waves, two blocks per CU, one barrier per 64-deep k-step, 2-stage
-// LDS-DMA ring, XOR swizzle on the source side), entry and split-K slice from blockIdx.y, fp32 tile to the entry's slab.
+// (2) the batched GEMM: the 160x160-tile, 4-wave, two-blocks-per-CU LDS-DMA ring loop of igemm_frag16.h (ring2_tile_loop, the
+// loop of igemm16.hip); work item and operand addressing from wino_loader.h; the tile goes to the item's slab.
 template <bool S16>   // S16: the tile goes to an f16 slab through the staged, coalesced epilogue of igemm_epilogue.h
 __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs p) {
-  constexpr int BM = 160, BN = 160, FM = 5, FN = 5;
+  constexpr int BM = kWinoTile, BN = kWinoTile, FM = 5, FN = 5;
   constexpr int A_BYTES = BM * 128, STAGE = (BM + BN) * 128;
   constexpr int NP = BM / 8 / 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -162,43 +133,19 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs p) {
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // Work item = (entry, split-K slice, tile), ordered entry-major with the second input's four entries first (their K is the
-  // other tensor's width, usually the longer loop).  The hardware deals workgroups to the 8 XCDs round-robin by linear id, so
-  // block b -> XCD b % 8 gets a CONTIGUOUS run of items: whole entries per XCD (two positions each at E = 16), i.e. every
-  // byte of U and V is fetched into exactly one L2.  (Tiles of one entry spread over all XCDs — the first version — pulled
-  // each V[pos] into all eight L2s: 260 MB through the fabric instead of 78 MB at the 16x16 level, 45 us instead of 36.)
-  const int ntile = p.tilesM * p.tilesN, W = p.E * p.splits * ntile;
-  const int n_extra = p.E - 16;
-  int item;
-  {
-    const int lin = blockIdx.x, xcd = lin & 7, j = lin >> 3;
-    const int WX = n_extra * p.splits * ntile, WM = W - WX;   // items of the second input's entries (first in item order) / of the 16 positions
-    if (((WX | WM) & 7) == 0) {
-      // every XCD takes its share of the long entries first, then its run of positions
-      const int xq = WX >> 3, mq = WM >> 3;
-      item = j < xq ? xcd * xq + j : WX + xcd * mq + (j - xq);
-    } else {
-      const int q = W >> 3, r = W & 7;
-      item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-  }
-  const int yes = item / ntile, tl = item - yes * ntile;
-  const int ye = yes / p.splits, split = yes - ye * p.splits;
-  const int entry = ye < n_extra ? 16 + ye : ye - n_extra;
+  const WinoItem it = wino_item(p, blockIdx.x);
+  const int entry = it.entry, cm0 = it.m0, cn0 = it.n0;
   const bool extra = entry >= 16;
   const int nk = extra ? p.nk2 : p.nk, nkps = extra ? p.nkps2 : p.nkps;
-  const int ks_begin = split * nkps;
+  const int ks_begin = it.split * nkps;
   const int nkl = min(nk, ks_begin + nkps) - ks_begin;
-  const int Kd = extra ? p.K2 : p.K;             // contraction width = W row length
-  const size_t slab_off = ((size_t)entry * p.splits + split) * p.T * p.N;
+  const int Kd = wino_kd(p, entry);
+  const size_t slab_off = ((size_t)entry * p.splits + it.split) * p.T * p.N;
 
-  const int tn = tl / p.tilesM, tm = tl - tn * p.tilesM;
-  const int cm0 = tm * BM, cn0 = tn * BN;
   const f16* Abase = extra ? p.in2 : p.V + (size_t)entry * p.T * p.K;
   const f16* Wbase = extra ? p.W2 : p.U + (size_t)entry * p.N * p.K;
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc((void*)Wbase, 0, 0x7FFFFFFF, 0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
   const int lrow = lane >> 3, lch = lane & 7;
 
   unsigned a_off[NP], w_off[NP];
@@ -206,91 +153,36 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs p) {
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int row = (wave * NP + i) * 8 + lrow;
-    const int m = cm0 + row;
-    a_c[i] = (lch ^ ((row >> 1) & 7)) * 8;
-    a_off[i] = OOB;
-    if (m < p.T) {
-      if (extra) {   // tile m -> pixel (2ty + a, 2tx + b) of in2
-        const int tpi = p.th * p.tw;
-        const int img = m / tpi, rem = m - img * tpi;
-        const int ty = rem / p.tw, tx = rem - ty * p.tw;
-        const int ab = entry - 16;
-        const int prow = img * p.H * p.W + (2 * ty + (ab >> 1)) * p.W + 2 * tx + (ab & 1);
-        a_off[i] = (unsigned)prow * (unsigned)p.lda2 * 2u;
-      } else {
-        a_off[i] = (unsigned)m * (unsigned)p.K * 2u;
-      }
-    }
-    const int n = cn0 + row;
-    w_off[i] = n < p.N ? (unsigned)n * (unsigned)Kd * 2u : OOB;
+    a_c[i] = igemm_swizzle_chunk(row, lch);
+    a_off[i] = wino_a_row(p, entry, cm0 + row);
+    w_off[i] = wino_w_row(p, entry, cn0 + row);
   }
   auto issue = [&](int g, int stage) __attribute__((always_inline)) {
     const int c0 = (ks_begin + g) * BK;
     char* sbase = smem + stage * STAGE;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int c = c0 + a_c[i];
-      const unsigned vo = (c < Kd && a_off[i] != OOB) ? a_off[i] + (unsigned)c * 2u : OOB;
+    for (int i = 0; i < NP; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsrcA, (__attribute__((address_space(3))) void*)(sbase + (wave * NP + i) * 1024), 16, vo, 0, 0, 0);
-    }
+          rsrcA, (__attribute__((address_space(3))) void*)(sbase + (wave * NP + i) * 1024), 16, wino_piece_offset(a_off[i], c0 + a_c[i], Kd), 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int c = c0 + a_c[i];
-      const unsigned vo = (c < Kd && w_off[i] != OOB) ? w_off[i] + (unsigned)c * 2u : OOB;
+    for (int i = 0; i < NP; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsrcW, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + (wave * NP + i) * 1024), 16, vo, 0, 0, 0);
-    }
+          rsrcW, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + (wave * NP + i) * 1024), 16, wino_piece_offset(w_off[i], c0 + a_c[i], Kd), 0, 0, 0);
   };
 
-  // weights are the MFMA A operand, tiles the B operand -> D[channel][tile row]
-  const int l15 = lane & 15, kg = lane >> 4;
-  const int sw = (lane >> 1) & 7;
-  const int koff0 = ((kg ^ sw) << 4), koff1 = (((4 + kg) ^ sw) << 4);
-  const int rowA = (wm * (BM / 2) + l15) * 128, rowB = A_BYTES + (wn * (BN / 2) + l15) * 128;
+  const Frag16Lanes fl = frag16_lanes(lane);
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+  frag16_zero(acc);
   if (nkl > 0) issue(0, 0);
-  for (int g = 0; g < nkl; ++g) {
-    wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-    if (g + 1 < nkl) issue(g + 1, (g + 1) & 1);
-    const char* sb = smem + (g & 1) * STAGE;
-    __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int koff = kk ? koff1 : koff0;
-      f16x8 wf[FN], xf[FM];
-#pragma unroll
-      for (int i = 0; i < FN; ++i) wf[i] = *(const f16x8*)(sb + rowB + i * 2048 + koff);
-#pragma unroll
-      for (int j = 0; j < FM; ++j) xf[j] = *(const f16x8*)(sb + rowA + j * 2048 + koff);
-      __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(3);
-    }
-  }
+  ring2_tile_loop<BM, BN, FM, FN, false>(smem, nkl, wm, wn, lane, issue, acc);
   const int row0 = wm * (BM / 2), col0 = wn * (BN / 2);
+  wait_lgkm0();
+  tick_barrier();   // every wave is done reading the ring
   if constexpr (S16) {
-    // f16 slab: accumulators -> f16 tile in LDS -> whole-row 16-byte stores (the plain-projection path of tile_epilogue)
-    wait_lgkm0();
-    tick_barrier();   // every wave is done reading the ring
-    IgemmArgs q{};
-    q.out = (f16*)p.slab + slab_off;
-    q.M = p.T; q.N = p.N; q.ldc = p.N; q.epi = 0; q.out_scale = 1.0f; q.dup = 0;
-    tile_epilogue<FM, FN, false, 256, BM, BN, false, false>(q, smem, acc, cm0, cn0, row0, col0, l15, kg, t, nullptr);
+    slab16_tile_store<FM, FN, 256, BM, BN>((f16*)p.slab + slab_off, p.T, p.N, smem, acc, cm0, cn0, row0, col0, fl.l15, fl.kg, t);
   } else {
     // fp32 tile to the slab, whole rows per store through LDS (an empty slice — more splits than k-steps — writes zeros)
-    wait_lgkm0();
-    tick_barrier();   // every wave is done reading the ring
-    slab_store_staged<FM, FN, 256, BM, BN, 80>(p.slab + slab_off, p.N, p.T, p.N, smem, acc, cm0, cn0, row0, col0, l15, kg, t);
+    slab_store_staged<FM, FN, 256, BM, BN, 80>(p.slab + slab_off, p.N, p.T, p.N, smem, acc, cm0, cn0, row0, col0, fl.l15, fl.kg, t);
   }
 }
 
@@ -486,7 +378,7 @@ __global__ __launch_bounds__(256) void upsample_gather_kernel(const UpGatherArgs
       const int yy = Y + ky - 1, xx = X + kx - 1;
       const bool ok = (unsigned)yy < (unsigned)H2 && (unsigned)xx < (unsigned)W2;
       const unsigned row = (unsigned)(img * p.H * p.W + (yy >> p.up) * p.W + (xx >> p.up));
-      const unsigned off = ok ? (row * (unsigned)p.ldp + (unsigned)((ky * 3 + kx) * p.C + c8 * 8)) * 2u : 0x80000000u;
+      const unsigned off = ok ? (row * (unsigned)p.ldp + (unsigned)((ky * 3 + kx) * p.C + c8 * 8)) * 2u : kIgemmOOB;
       v[ky * 3 + kx].v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
     }
   float acc[8];

@@ -9,7 +9,10 @@
    elements that close() of tests/test_hip_kernels.py still accepts is printed: what the tolerance lets through.
 3. The operand addressing the three tile kernels share (rcdms_amd/csrc/igemm_loader.h) runs on the CPU
    (tools/igemm_loader_host.cpp): the operands gathered through its offsets are the model's A and W, the tile order is a
-   bijection, and one moved border tap breaks the comparison."""
+   bijection, and one moved border tap breaks the comparison.
+4. The same for the batched GEMM of the Winograd conv (rcdms_amd/csrc/wino_loader.h, the tool's `wino` mode): every
+   (entry, split, tile) is dealt to exactly one block on both paths of the dealing, and the gathered operands are the
+   model's V / U panels and the second input's parity pixels."""
 import os
 import subprocess
 
@@ -425,3 +428,80 @@ def test_mutation_moved_border_tap(hip, loader_tool):
     moved = rec.copy()
     moved[border, 6] = rec[below, 6]
     assert not check(moved)
+
+
+# ---- 4. the Winograd GEMM's work dealing and operand addressing (csrc/wino_loader.h), through the same tool ---------------
+def run_wino_loader(tool, n_img, H, W, K, K2, N, lda2, splits, tiles_m, tiles_n, nk):
+    args = ["wino"] + [str(v) for v in (n_img, H, W, K, K2, N, lda2, splits, tiles_m, tiles_n, nk)]
+    r = subprocess.run([tool] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")
+    return np.fromstring(r.stdout.decode(), dtype=np.int64, sep=" ").reshape(-1, 7)
+
+
+# (K2, splits, tiles_m, tiles_n, the dealing's path).  WX = (E - 16) * splits * tiles items of the second input, WM = 16 *
+# splits * tiles of the positions: both multiples of 8 -> every XCD takes its share of each ("shares"), else one contiguous
+# run per XCD over all items ("runs").  E = 16 has WX = 0 and WM a multiple of 16: always "shares"; the last case is the
+# same 1 x 3 tiling with a second input, where WX = 12.
+@pytest.mark.parametrize("K2,splits,tiles_m,tiles_n,path", [(128, 2, 2, 2, "shares"), (0, 1, 1, 3, "shares"), (128, 3, 1, 1, "runs"),
+                                                           (128, 1, 1, 3, "runs")])
+def test_wino_items_are_a_bijection(loader_tool, K2, splits, tiles_m, tiles_n, path):
+    E, tiles = (20 if K2 else 16), tiles_m * tiles_n
+    WX, WM = (E - 16) * splits * tiles, 16 * splits * tiles
+    assert ("shares" if (WX | WM) % 8 == 0 else "runs") == path
+    rec = run_wino_loader(loader_tool, 2, 4, 4, 64, K2, 16, K2 + 16 if K2 else 0, splits, tiles_m, tiles_n, 0)
+    assert (rec[:, 0] == 3).all() and (rec[:, 1] == np.arange(E * splits * tiles)).all() and (rec[:, 6] == 0).all()
+    hit = sorted(zip(rec[:, 4].tolist(), rec[:, 5].tolist(), rec[:, 2].tolist(), rec[:, 3].tolist()))
+    assert hit == [(e, s, i * 160, j * 160) for e in range(E) for s in range(splits) for i in range(tiles_m) for j in range(tiles_n)]
+    if path == "runs" and (WX + WM) % 8:                     # a short last run: the XCDs' run lengths differ by one, longer first
+        order = {(e, s, m0, n0): k for k, (e, s, m0, n0) in enumerate(
+            ((16 + e if e < E - 16 else e - (E - 16)), s, i * 160, j * 160)
+            for e in range(E) for s in range(splits) for j in range(tiles_n) for i in range(tiles_m))}
+        item = np.array([order[(e, s, m0, n0)] for e, s, m0, n0 in zip(rec[:, 4].tolist(), rec[:, 5].tolist(), rec[:, 2].tolist(), rec[:, 3].tolist())])
+        runs = [item[x::8] for x in range(8)]
+        assert all((np.diff(r) == 1).all() for r in runs)                      # each XCD: consecutive items
+        assert [len(r) for r in runs] == sorted((len(r) for r in runs), reverse=True) and len(runs[0]) - len(runs[7]) == 1
+        assert all(runs[x + 1][0] == runs[x][-1] + 1 for x in range(7))
+
+
+def test_wino_loader_operands(loader_tool):
+    """n_img = 2, H = W = 4 (T = 8 tiles), K = 64, K2 = 128, N = 16, two k-steps walked for every entry: gathering through the
+    printed offsets gives the model's V / U panels and, for entries 16 + 2a + b, the (2ty + a, 2tx + b) pixels of the second
+    input against W2; tile rows past T, weight rows past N and (positions, second k-step) channels past K are out of bounds."""
+    n_img, H, W, K, K2, N, nk = 2, 4, 4, 64, 128, 16, 2
+    lda2, T = K2 + 16, n_img * (H // 2) * (W // 2)
+    c = X.wino_case(n_img, H, W, K, K2, N, 0, 1.0, False)
+    _, _, V, U = X.wino_model(c["x_eff"], c["w"], 1, c["x2"], c["w2"])
+    rec = run_wino_loader(loader_tool, n_img, H, W, K, K2, N, lda2, 1, 1, 1, nk)
+    items = rec[rec[:, 0] == 3]
+    assert sorted(items[:, 4].tolist()) == list(range(20)) and (items[:, 2] == 0).all() and (items[:, 3] == 0).all()
+    raw_x2 = padded_rows(c["x2"].reshape(-1, K2), lda2)
+
+    def panel(mat):              # [rows][Kd] -> what the tile sees: [160][nk * 64], zeros past the rows and past Kd
+        out = np.zeros((160, nk * X.BK))
+        out[:mat.shape[0], :mat.shape[1]] = mat
+        return out
+
+    seen_oob = set()
+    for lin, entry in zip(items[:, 1].tolist(), items[:, 4].tolist()):
+        mine = rec[(rec[:, 0] != 3) & (rec[:, 1] == lin)].copy()
+        mine[:, 1] = 0
+        act, wgt = mine[mine[:, 0] <= 1], mine[mine[:, 0] == 2]
+        if entry < 16:
+            a_kind, raw_a, want_a = 0, V[entry // 4, entry % 4].reshape(-1), panel(V[entry // 4, entry % 4])
+            raw_w, want_w, Kd = U[entry // 4, entry % 4].reshape(-1), panel(U[entry // 4, entry % 4]), K
+        else:
+            a, b = (entry - 16) >> 1, (entry - 16) & 1
+            a_kind, raw_a, want_a = 1, raw_x2, panel(c["x2"][:, a::2, b::2].reshape(T, K2))
+            raw_w, want_w, Kd = c["w2"].reshape(-1), panel(c["w2"]), K2
+        assert (act[:, 0] == a_kind).all()
+        rows_of = lambda lin_, row: row
+        assert _gather(act, {a_kind: raw_a}, want_a, rows_of, 160, nk), f"entry {entry}: the gathered A operand is not the model's"
+        assert _gather(wgt, {2: raw_w}, want_w, rows_of, 160, nk), f"entry {entry}: the gathered weight operand is not the model's"
+        for r, rows, what in ((act, T, "tile row past T"), (wgt, N, "weight row past N")):
+            inside = (r[:, 3] < rows) & (r[:, 2] * X.BK + r[:, 5] < Kd)
+            assert (r[inside, 6] >= 0).all() and (r[~inside, 6] == -1).all()
+            if (r[:, 3] >= rows).any():
+                seen_oob.add(what)
+            if (r[:, 2] * X.BK + r[:, 5] >= Kd).any():
+                seen_oob.add("channel chunk past Kd")
+    assert seen_oob == {"tile row past T", "weight row past N", "channel chunk past Kd"}

@@ -12,10 +12,21 @@
 //                              first of its eight channels within the k-step's 64 (the swizzle), byte offset or -1 (out of bounds)
 //   2 lin ks row lch c off     weight piece, likewise
 // With nk = 0 only the tile lines are printed.  Exit status 2: bad arguments.
+//
+// Winograd mode — the batched GEMM of the Winograd conv3x3 (rcdms_amd/csrc/wino_loader.h, wino.hip wino_gemm_kernel):
+//   igemm_loader_host wino n_img H W K K2 N lda2 splits tilesM tilesN nk
+// (K2 = 0: no second input, 16 entries; else 20.  tilesM / tilesN are taken as given, like the launch's.)  Per block `lin`:
+//   3 lin m0 n0 entry split 0  the work item: entry, split-K slice, first tile row and column
+//   0|1 lin ks row lch c off   piece of the entry's A operand at k-step ks < nk: 0 = V[entry] (offset inside that position's
+//                              [T][K] panel), 1 = the second input in2 (entries 16 + 2a + b)
+//   2 lin ks row lch c off     piece of its weight operand: inside U[entry] ([N][K]), or W2 ([N][K2]) for entries >= 16
+// nk is the number of k-steps WALKED for every item (the kernel walks its slice of K / 64 or K2 / 64): a step past an entry's
+// contraction width must print as out of bounds.  nk = 0: item lines only.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
-#include "igemm_loader.h"
+#include "wino_loader.h"
 
 namespace {
 
@@ -57,9 +68,46 @@ bool walk_tile(const IgemmArgs& p, int bm, int bn) {
   return false;
 }
 
+int wino_main(int argc, char** argv) {
+  if (argc != 13) {
+    fprintf(stderr, "usage: igemm_loader_host wino n_img H W K K2 N lda2 splits tilesM tilesN nk\n");
+    return 2;
+  }
+  int v[13];
+  for (int i = 2; i < 13; ++i) v[i] = atoi(argv[i]);
+  WinoArgs p{};
+  p.n_img = v[2]; p.H = v[3]; p.W = v[4]; p.K = v[5]; p.K2 = v[6]; p.N = v[7]; p.lda2 = v[8]; p.splits = v[9];
+  p.tilesM = v[10]; p.tilesN = v[11];
+  const int nk = v[12];
+  if (p.n_img <= 0 || p.H <= 0 || p.W <= 0 || (p.H & 1) || (p.W & 1) || p.K <= 0 || (p.K & 63) || p.K2 < 0 || (p.K2 & 63) || p.N <= 0 ||
+      (p.K2 && p.lda2 < p.K2) || p.splits <= 0 || p.tilesM <= 0 || p.tilesN <= 0 || nk < 0) {
+    fprintf(stderr, "igemm_loader_host wino: H and W even, K and K2 multiples of 64, lda2 >= K2\n");
+    return 2;
+  }
+  p.th = p.H / 2; p.tw = p.W / 2; p.T = p.n_img * p.th * p.tw;
+  p.E = p.K2 ? 20 : 16;
+  for (int lin = 0; lin < p.E * p.splits * p.tilesM * p.tilesN; ++lin) {
+    const WinoItem it = wino_item(p, lin);
+    printf("3 %d %d %d %d %d 0\n", lin, it.m0, it.n0, it.entry, it.split);
+    const int Kd = wino_kd(p, it.entry);
+    for (int ks = 0; ks < nk; ++ks) {
+      for (int op = 0; op < 2; ++op)
+        for (int row = 0; row < kWinoTile; ++row) {
+          const unsigned r_off = op ? wino_w_row(p, it.entry, it.n0 + row) : wino_a_row(p, it.entry, it.m0 + row);
+          for (int lch = 0; lch < 8; ++lch) {
+            const int c = igemm_swizzle_chunk(row, lch);
+            printf("%d %d %d %d %d %d %lld\n", op ? 2 : it.entry >= 16 ? 1 : 0, lin, ks, row, lch, c, shown(wino_piece_offset(r_off, ks * BK + c, Kd)));
+          }
+        }
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "wino")) return wino_main(argc, argv);
   if (argc != 23) {
     fprintf(stderr, "usage: igemm_loader_host TAPS BM BN M N Cin Ktot Hi Wi Ho Wo stride up pad lda nk nk1 Cin2 lda2 ph_rows tilesM tilesN\n");
     return 2;

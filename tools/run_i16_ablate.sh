@@ -1,5 +1,7 @@
 # Ablation of the 160x160 kernel (tools/kbench.py, variant 9): product build vs the -DRCDM_I16_ABLATE debug builds
-# (rcdms_amd.build.build_variant): 1 = no epilogue, 2 = epilogue without global stores, 9 = no epilogue and no DMA
+# (rcdms_amd.build.build_variant): 1 = no epilogue, 2 = epilogue without global stores, 9 = no epilogue and no DMA.
+# Bit 8 is the ABLATE argument igemm16.hip gives ring2_tile_loop (csrc/igemm_frag16.h); the Winograd GEMM, which runs the
+# same loop, passes 0: these figures are about variant 9 only.
 O=gpurun_out/i16_ablate.log; : > $O
 for lib in ${LIBS:-hip i16a1 i16a2 i16a9}; do
   echo "== lib $lib" >> $O
